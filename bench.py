@@ -10,6 +10,12 @@ Workload (BASELINE.json configs[1]): Fundus target 0 --ram --rec --consistency k
 accumulate, batch 8 = [2,3,3] per GPU at 400x400x3, synthetic images (no dataset is available offline),
 random-init weights.  Weak scaling: every rank runs its own batch of 8; gradients are averaged with RCCL.
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the steps and prints the headline (`value` images/s, `ms_per_step`).  --full adds everything
+else the line can carry, each still switchable off with its --no-* option: the box probes and shader clock, the live PMC / SQ
+counter runs, the whole-step and per-family rooflines with the ablation that picks the headline family, the fp32 leg, the
+4-process saturation run, the CPU baseline and the per-bucket gradient exchange.  --dump-outputs DIR writes what the last timed
+step computed (losses, parameters after Adam, gradients, BatchNorm buffers, network outputs) as float32 .npy files.
 """
 import argparse
 import json
@@ -200,7 +206,7 @@ def collect_live_pmc(B, dtype, size, config='C2', timeout=240):
     try:
         cmd = [exe, '-i', os.path.join(ROOT, 'scripts', 'pmc_hbm.txt'), '--kernel-trace', '-M', '--output-format', 'csv', '-d', outdir, '-o', 'p',
                '--', sys.executable, os.path.abspath(__file__), '--steps', '3', '--warmup', '1', '--config', config, '--size', str(size), '--dtype', dtype,
-               '--no-cpu-baseline', '--no-fp32-leg', '--no-ablation', '--no-live-pmc', '--no-saturation']
+               '--full', '--no-cpu-baseline', '--no-fp32-leg', '--no-ablation', '--no-live-pmc', '--no-saturation']
         env = dict(os.environ, TMPDIR='/tmp', RD_BENCH_CHILD='1')
         for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'RD_FORCE_DDP'):
             env.pop(k, None)
@@ -392,6 +398,29 @@ def time_steps(step, n, warm=3):
         step()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n * 1e3
+
+
+DUMP_SAMPLE = 1 << 21          # values kept of a dumped network output larger than this: a fixed, seeded sample (the dump stays < 64 MB)
+
+
+def dump_outputs(ts, d):
+    """--dump-outputs: what the LAST timed step handed its caller, as float32 .npy files under d -- the loss terms loss_dict() reads
+    (losses[:6]) and the per-domain restoration MSEs, the parameters after Adam, that step's gradients, the BatchNorm buffers (sorted by
+    module and key), the segmentation logits and the restoration output of the network (NHWC, padding channels dropped).  The
+    parameters and gradients are written whole (3.8 M values each); a network output of more than DUMP_SAMPLE values is stored as the
+    values at DUMP_SAMPLE sorted positions drawn by RandomState(0), so the same workload always samples the same positions."""
+    os.makedirs(d, exist_ok=True)
+    bank = ts.bank
+    bufs = [bank.buffers[k].reshape(-1).double() for k in sorted(bank.buffers)]
+    outs = {'losses': ts.losses[:6], 'rec_mse': ts.rec_mse, 'params': bank.params, 'grads': bank.grads,
+            'bn_buffers': torch.cat(bufs) if bufs else torch.zeros(0), 'seg_logits': ts.logits.buf[..., :ts.K],
+            'rec_output': ts.rec_logits.buf[..., :ts.c]}
+    torch.cuda.synchronize()
+    for name, t in outs.items():
+        a = t.detach().float().cpu().numpy()
+        if name in ('seg_logits', 'rec_output') and a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def step_cost_by_ablation(ts, fams, steps=20):
@@ -656,6 +685,9 @@ def main():
     ap.add_argument('--launch-ranks', action='store_true', help='start the ranks as a child torchrun even for --gpus 1 (what --gpus N > 1 does by itself when no launcher set WORLD_SIZE)')
     ap.add_argument('--no-box', action='store_true', help='skip the two micro-kernels that report this box\'s copy rate / MFMA rate (`box`, `value_normalised`)')
     ap.add_argument('--no-live-pmc', action='store_true', help='take the HBM traffic figures from the committed profiles/dominant_kernel_pmc.json instead of measuring them in a rocprofv3 child run')
+    ap.add_argument('--full', action='store_true', help='after the headline, everything else the line reports (box probes, counters, rooflines, ablation, fp32 leg, '
+                                                         'saturation, CPU baseline, gradient exchange); the --no-* options switch parts of it off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as float32 DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
 
     if (args.gpus > 1 or args.launch_ranks) and 'WORLD_SIZE' not in os.environ:
@@ -742,11 +774,13 @@ def main():
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ts, args.dump_outputs)
     losses = ts.loss_dict()
     assert np.isfinite(losses['loss']), losses
     # data parallel: each gradient bucket's all-reduce on its own (nothing else on the GPU), so that a multi-GPU run says
     # what the exchange costs next to what the step hides of it
-    exchange = bucket_allreduce_us(runner, world) if runner is not None else None
+    exchange = bucket_allreduce_us(runner, world) if (args.full and runner is not None) else None
     # every rank's lane / queue layout (streams measured to run beside each other, compute-unit budgets), gathered on rank 0
     layouts = [ts.lane_layout()]
     if world > 1:
@@ -768,7 +802,7 @@ def main():
                        'ram_pipelined': not (args.graph or args.no_pipeline), 'launch': 'rd_run_list (one native call per step)' if not args.graph else 'hipGraph replay',
                        'final_loss': round(losses['loss'], 4)},
         }
-        if not args.no_box and not _under_profiler():
+        if args.full and not args.no_box and not _under_profiler():
             try:
                 out['box'] = box_probe(dev)
                 out['value_normalised'] = round(out['value'] / out['box']['speed_vs_ref'], 2)
@@ -778,12 +812,13 @@ def main():
                 out['box'] = {'error': repr(e)[:200]}
         # HBM traffic measured by this run (a rocprofv3 child of the same command, after the timed region); single process only: under
         # torchrun the committed summary is used
-        if world == 1 and runner is None and not args.graph and not args.no_live_pmc:
+        if args.full and world == 1 and runner is None and not args.graph and not args.no_live_pmc:
             collect_live_pmc(B, args.dtype, Sz, args.config)
             if args.config == 'C2':
                 collect_live_sq(args.dtype, Sz)
-        out['roofline_step'] = whole_step_roofline(B, Sz, out['ms_per_step'], args.dtype)
-        if args.dtype == 'bf16':
+        if args.full:
+            out['roofline_step'] = whole_step_roofline(B, Sz, out['ms_per_step'], args.dtype)
+        if args.full and args.dtype == 'bf16':
             roofs = {}
             for fam in FAMILIES:
                 roofs[fam] = kernel_roofline(ts, fam, eager=not args.graph)
@@ -812,9 +847,9 @@ def main():
                     roofs[f]['step_cost_ms'] = cost[f]
             for fam, r in roofs.items():
                 out['roofline' if fam == dominant else 'roofline_' + fam] = r
-        if world == 1 and args.dtype == 'bf16' and not args.no_fp32_leg:
+        if args.full and world == 1 and args.dtype == 'bf16' and not args.no_fp32_leg:
             out['extra'] = {'fp32': fp32_leg(params0, bs, Sz, dev, src, trg, lam, mask, dataset=dataset, num_classes=K, consistency=cfg['consistency'], lr=cfg['lr'])}
-        if world == 1 and runner is None and args.config == 'C2' and Sz == 400 and args.dtype == 'bf16' and not args.no_saturation and not _under_profiler() \
+        if args.full and world == 1 and runner is None and args.config == 'C2' and Sz == 400 and args.dtype == 'bf16' and not args.no_saturation and not _under_profiler() \
                 and os.environ.get('RD_BENCH_CHILD') != '1':
             # how much of the gap to the roofs is dependency bubbles and how much is kernels: the same step from 4 processes at once on this GPU
             try:
@@ -826,7 +861,7 @@ def main():
             except Exception as e:                                    # the figure is diagnostic: never lose the line over it
                 out['gpu_saturated_images_per_s'] = None
                 out['gpu_saturated'] = {'error': repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(host_inputs, bs, dataset, K, cfg['consistency'], cfg['lr'])
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -7,7 +7,7 @@ P=scripts/probe/swap_probe.bin
   echo "== three processes at once"
   for k in 1 2 3; do (timeout 200 $P 20 20000 > $O/swap_$k.txt 2>&1) & done; wait
   cat $O/swap_1.txt $O/swap_2.txt $O/swap_3.txt ) > $O/swap_probe.txt 2>&1
-Q="--no-cpu-baseline --no-fp32-leg --no-ablation --no-live-pmc --no-saturation"
+Q="--full --no-cpu-baseline --no-fp32-leg --no-ablation --no-live-pmc --no-saturation"
 for i in 1 2; do
   timeout 300 python3 bench.py --steps 20 --warmup 5 $Q > $O/bench_short_$i.json 2> $O/bench_short_$i.err
   timeout 300 python3 bench.py --steps 100 --warmup 10 $Q > $O/bench_long_$i.json 2> $O/bench_long_$i.err

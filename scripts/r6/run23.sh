@@ -1,9 +1,9 @@
 #!/bin/bash
-mkdir -p gpurun_out/r6p
+O=${1:?usage: run23.sh OUTDIR}; mkdir -p $O
 for i in 1 2 3; do
-timeout 600 python3 bench.py --no-cpu-baseline --no-fp32-leg --no-ablation --no-live-pmc --no-saturation > gpurun_out/r6p/bench.json 2> gpurun_out/r6p/bench.err
+timeout 600 python3 bench.py --full --no-cpu-baseline --no-fp32-leg --no-ablation --no-live-pmc --no-saturation > $O/bench.json 2> $O/bench.err
 python3 -c "
-import json; d=json.loads(open('gpurun_out/r6p/bench.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], json.dumps(d['box']['shader_ghz'])[:120])"
+import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], json.dumps(d['box']['shader_ghz'])[:120])"
 done
 timeout 600 python3 -m pytest tests/test_gpu_bench.py -m gpu -x -q 2>&1 | tail -3
 export RAMDSIR_DEBUG_LIB=1 RD_CONV_WS_TRACE_MIN=1

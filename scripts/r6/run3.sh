@@ -15,7 +15,7 @@ RD_REGEN_BITWISE=1 timeout 600 python3 -m pytest tests/test_gpu_bitwise_golden.p
 cp gpurun_out/hip_bitwise.json $O/hip_bitwise.json
 timeout 2400 python3 -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1
 tail -15 $O/pytest_gpu.txt
-timeout 600 python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout 600 python3 bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python3 -c "
 import json
 d = json.loads(open('$O/bench.json').read().strip().splitlines()[-1])

@@ -5,8 +5,8 @@ O=gpurun_out/r6h; mkdir -p $O
 timeout 2400 python3 -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1; tail -6 $O/pytest_gpu.txt
 bash scripts/collect_profiles.sh > $O/collect.log 2>&1
 cp gpurun_out/profiles_run/bench.json $O/bench.json
-for c in C3 C5 F256; do timeout 600 python3 bench.py --config $c --no-cpu-baseline --no-ablation --no-saturation > $O/bench_$c.json 2> $O/bench_$c.err; done
-timeout 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-leg --no-ablation --no-live-pmc --no-saturation > $O/bench_driver_form.json 2>/dev/null
+for c in C3 C5 F256; do timeout 600 python3 bench.py --config $c --full --no-cpu-baseline --no-ablation --no-saturation > $O/bench_$c.json 2> $O/bench_$c.err; done
+timeout 300 python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-fp32-leg --no-ablation --no-live-pmc --no-saturation > $O/bench_driver_form.json 2>/dev/null
 timeout 300 python3 scripts/layer_bench.py bf16 400 250 > $O/layer_bench.txt 2>&1
 timeout 300 python3 scripts/contended_ops.py 30 > $O/contended_ops.txt 2>&1
 # stamps inside conv_ws_kernel's steps (debug library), forward and gradient launch of one layer; the gradient launches on the whole device

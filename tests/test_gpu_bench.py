@@ -1,4 +1,4 @@
-"""-m gpu: bench.py's data-parallel path on one GPU (RD_FORCE_DDP=1: a one-rank RCCL process group), so that the four-segment launch
+"""-m gpu: the plain bench line and --dump-outputs; bench.py's data-parallel path on one GPU (RD_FORCE_DDP=1: a one-rank RCCL process group), so that the four-segment launch
 with the three gradient-bucket exchanges (ramdsir/ddp.py; reference: nn.DataParallel's gradient reduction, code/train.py:205-208) is
 run and TIMED on every driver round even when no multi-GPU node is available, and the bench line's multi-GPU fields are exercised."""
 import json
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_on_the_forced_data_parallel_path():
     env = dict(os.environ, RD_FORCE_DDP='1', MASTER_ADDR='127.0.0.1', MASTER_PORT='29541')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '3', '--no-cpu-baseline', '--no-fp32-leg',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '3', '--full', '--no-cpu-baseline', '--no-fp32-leg',
                         '--no-ablation'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith('{')][-1]
@@ -42,7 +42,7 @@ def test_bench_lines_of_the_other_baseline_configs(name, dataset, split, side):
     """bench.py --config: the workloads BASELINE.json lists beside the metric's own (C3 Prostate 5 x 2 at 384 with softmax / CE / dice_multi,
     train.py:39-45,363-465; C5 512 x 512 with 4 domains; F256 the reference's native Fundus shape, train.py:35,541) give a line with the
     same fields: throughput of the whole step at that shape, its roofline position, the workload named in config."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', name, '--steps', '4', '--warmup', '2', '--no-cpu-baseline',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', name, '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline',
                         '--no-fp32-leg', '--no-ablation', '--no-live-pmc', '--no-saturation'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith('{')][-1])
@@ -60,7 +60,7 @@ def test_bench_launches_its_own_ranks_when_no_launcher_did():
     forces the same path for N = 1 (this box has one GPU); with --gpus 2 here the ranks must fail inside the runtime / RCCL -- not with
     bench.py's own "WORLD_SIZE is 1" refusal.  Reference parallelism: nn.DataParallel, code/train.py:205-208."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'RD_FORCE_DDP')}
-    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-fp32-leg', '--no-ablation',
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-fp32-leg', '--no-ablation',
             '--no-live-pmc', '--no-saturation']
     r = subprocess.run(base + ['--gpus', '1', '--launch-ranks'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -74,3 +74,25 @@ def test_bench_launches_its_own_ranks_when_no_launcher_did():
         err = r2.stderr.decode()
         assert r2.returncode != 0
         assert 'runs one rank per GPU but WORLD_SIZE is' not in err, err[-2000:]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline fields only; --dump-outputs writes what the last timed
+    step computed as float32 .npy files (the losses agree with the line's final_loss, 64 MB at most in all)."""
+    import numpy as np
+    d = tmp_path / 'out'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--dump-outputs', str(d)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith('{')][-1])
+    assert line['metric'] == 'images/sec (seg+rec+RAM step)' and line['unit'] == 'images/s' and line['higher_is_better'] is True
+    assert line['dtype'] == 'bf16' and line['steps'] == 5 and line['ms_per_step'] > 0
+    assert abs(line['value'] - 8 * 1e3 / line['ms_per_step']) < 0.01 * line['value']
+    assert not any(k in line for k in ('box', 'roofline', 'roofline_step', 'extra', 'cpu_baseline', 'gpu_saturated'))
+    files = {f.name: np.load(f) for f in d.iterdir()}
+    assert set(files) == {'losses.npy', 'rec_mse.npy', 'params.npy', 'grads.npy', 'bn_buffers.npy', 'seg_logits.npy', 'rec_output.npy'}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    assert files['params.npy'].shape == (3800021,) and files['losses.npy'].shape == (6,) and files['rec_mse.npy'].shape == (3,)
+    loss = float(files['losses.npy'][5]) + 0.1 * float(files['rec_mse.npy'].astype(np.float64).sum())
+    assert abs(loss - line['config']['final_loss']) < 1e-3
