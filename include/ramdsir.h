@@ -471,6 +471,81 @@ void rd_run_list_fork_counts(long long* bound, long long* recorded);
  * or a lane entry with wait_main, follows before the main stream is given anything else or joins a lane).  Host logic only. */
 int rd_run_list_fork_plan(const rd_launch_t* ops, int n, unsigned char* carries);
 
+/* ------------------------------------------------------------------------------------------------
+ * GPU-resident training data (train.py --gpu_data, ramdsir/gpu_data.py): the decoded pixels of every image training can touch
+ * stay in device memory, the host only draws the random numbers, and ONE launch per step does all the per-sample pixel work of
+ * the host path's DataLoader workers -- for the whole step's batch, all domains concatenated, on the caller's stream, with no
+ * host-device synchronisation.
+ *
+ * rd_fundus_batch replaces Resize(256) + RandomScaleCrop(256) (code/dataset/transform.py:163-204) and the per-sample work of
+ * Fundus_Multi.__getitem__ (code/dataset/fundus.py:197-240): image -> bilinear S x S -> (with the drawn factors) bilinear sw x sh
+ * -> crop (cx, cy, S x S); the mask through the same geometry with nearest sampling, then [cup = g <= 50, disc = g <= 200]; the
+ * partner -> bilinear S x S; lam.  The arithmetic is Pillow's 8-bit resampling (Resample.c), integer only, so the result is BIT-
+ * IDENTICAL to the host path: per axis a table (ramdsir/resample.py axis_table) at an int32 offset of `tables`:
+ *   [n_in, n_out, ksize, 0] xmin[n_out] cnt[n_out] k[n_out][ksize] nearest[n_out]
+ * out[i] = clamp((2^21 + sum_{t < cnt[i]} in[xmin[i] + t] * k[i][t]) >> 22, 0, 255), the horizontal pass first and rounded to
+ * uint8, nearest[i] the source index Image.resize(NEAREST) takes.  "No scaling" is sw = sh = S with the identity tables of S -> S
+ * (which reproduce their input exactly).  One workgroup per (sample, band of band_rows output rows, image / partner); the stage-1
+ * rows a band needs live in LDS: (src_rows + 2 mid_rows) * S * 3 bytes, bounds the caller derives from the tables
+ * (ramdsir/resample.py max_window).
+ * Outputs: src, trg uint8 [B][S][S][3]; lam fp32 [B]; mask fp32 [B][2][S][S] -- what train.py's on_device() makes of the host
+ * path's batches. */
+typedef struct {
+    int64_t off;                /* byte offset of the HWC RGB pixels in rd_fundus_batch_t.pixels */
+    int64_t mask_off;           /* byte offset of the gray mask (H x W) in .masks, -1: none (partner-only images) */
+    int32_t h, w;
+    int32_t tab_x, tab_y;       /* tables w -> S (x) and h -> S (y) */
+} rd_aug_image_t;
+
+typedef struct {
+    int32_t img, partner;       /* image slots */
+    int32_t tab_x, tab_y;       /* tables S -> sw (x) and S -> sh (y) */
+    int32_t sw, sh;             /* the scaled size (S, S: the coin said no) */
+    int32_t cx, cy;             /* crop offset, 0 <= cx <= sw - S, 0 <= cy <= sh - S */
+    float lam;
+    int32_t pad_;
+} rd_fundus_sample_t;
+
+typedef struct {
+    const uint8_t* pixels;
+    const uint8_t* masks;
+    const rd_aug_image_t* images;   /* device array [n_images] */
+    const int32_t* tables;
+    uint8_t* src;
+    uint8_t* trg;
+    float* lam;
+    float* mask;
+    int32_t n_images;
+    int32_t S;                  /* output size (256) */
+    int32_t id_x, id_y;         /* tables S -> S (partner's second stage) */
+    int32_t band_rows, src_rows, mid_rows;
+    int32_t pad_;
+} rd_fundus_batch_t;
+/* samples_host: B HOST records (read before the call returns: they travel as kernel arguments, RD_AUG_CHUNK per launch).  Returns
+ * -1 for an invalid descriptor or record. */
+#define RD_AUG_CHUNK 48
+int rd_fundus_batch(const rd_fundus_batch_t* p, const rd_fundus_sample_t* samples_host, int B, void* stream);
+
+/* rd_prostate_batch replaces the per-sample work of Prostate_Multi.__getitem__ (code/dataset/prostate.py:167-188): gathers the
+ * resident fp32 (S, S, 3) slices of the images and partners and the masks (uint8 labels, widened to int64), and writes lam --
+ * exactly what the host path's collated batches hold: src, trg fp32 [B][S][S][3], lam fp32 [B], mask int64 [B][S][S]. */
+typedef struct {
+    int32_t img, partner;       /* slice slots (img must have a mask) */
+    float lam;
+    int32_t pad_;
+} rd_prostate_sample_t;
+
+typedef struct {
+    const float* slices;        /* [n_slices][S][S][3] */
+    const uint8_t* masks;       /* [n_slices][S][S] */
+    float* src;
+    float* trg;
+    float* lam;
+    int64_t* mask;
+    int32_t n_slices, S;
+} rd_prostate_batch_t;
+int rd_prostate_batch(const rd_prostate_batch_t* p, const rd_prostate_sample_t* samples_host, int B, void* stream);
+
 /* Measurement only (bench.py `box`): what this box's GPU sustains on two fixed micro-kernels, so that a bench line can be compared across
  * boxes of a pool whose clocks differ by a few per cent.  No reference counterpart (the reference publishes no throughput: BASELINE.md).
  *   which 0: streaming copy of n bytes (n % 16 == 0) from a to b, 16 B per lane, 8 workgroups of 256 threads per CU;

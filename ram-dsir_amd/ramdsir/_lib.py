@@ -80,6 +80,32 @@ class RdPackEntry(C.Structure):
                 ('transpose', i32), ('RowPad', i32), ('ColPad', i32)]
 
 
+AUG_CHUNK = 48         # RD_AUG_CHUNK
+
+
+class RdAugImage(C.Structure):
+    _fields_ = [('off', i64), ('mask_off', i64), ('h', i32), ('w', i32), ('tab_x', i32), ('tab_y', i32)]
+
+
+class RdFundusSample(C.Structure):
+    _fields_ = [('img', i32), ('partner', i32), ('tab_x', i32), ('tab_y', i32), ('sw', i32), ('sh', i32), ('cx', i32), ('cy', i32),
+                ('lam', f32), ('pad_', i32)]
+
+
+class RdFundusBatch(C.Structure):
+    _fields_ = [('pixels', vp), ('masks', vp), ('images', vp), ('tables', vp), ('src', vp), ('trg', vp), ('lam', fp), ('mask', fp),
+                ('n_images', i32), ('S', i32), ('id_x', i32), ('id_y', i32), ('band_rows', i32), ('src_rows', i32), ('mid_rows', i32),
+                ('pad_', i32)]
+
+
+class RdProstateSample(C.Structure):
+    _fields_ = [('img', i32), ('partner', i32), ('lam', f32), ('pad_', i32)]
+
+
+class RdProstateBatch(C.Structure):
+    _fields_ = [('slices', fp), ('masks', vp), ('src', fp), ('trg', fp), ('lam', fp), ('mask', vp), ('n_slices', i32), ('S', i32)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -144,6 +170,8 @@ _SIGS = {
     'rd_run_list_fork_counts': (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     'rd_run_list_fork_plan': (C.c_int, [C.POINTER(RdLaunch), C.c_int, C.POINTER(C.c_ubyte)]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
+    'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),
+    'rd_prostate_batch': (C.c_int, [C.POINTER(RdProstateBatch), C.POINTER(RdProstateSample), C.c_int, vp]),
 }
 
 _lib = None

@@ -83,6 +83,9 @@ def parse_args(argv=None):
     p.add_argument('--log_every', type=int, default=20)
     p.add_argument('--num_workers', type=int, default=8)
     p.add_argument('--max_iters', type=int, default=None, help='stop early (smoke runs)')
+    p.add_argument('--gpu_data', action='store_true',
+                   help='decode the training images once and keep them in device memory; the augmentation runs as one HIP launch per '
+                        'step (bit-identical to the host path with --num_workers 0, which then only sizes the preload thread pool)')
     return p.parse_args(argv)
 
 
@@ -180,6 +183,43 @@ def save_checkpoint(path, encoder, seg_decoder, rec_decoder):
                 'rec_decoder_state_dict': rec_decoder.state_dict()}, path)
 
 
+def make_loaders(args, data_root, world, rank, bsl, domain_idx_list):
+    """train.py:554-560: one loader per training domain, cycled except the longest.  --gpu_data: the same construction over the
+    parameter datasets of ramdsir/gpu_data.py, loaded in this process.  Returns (raw loaders, samplers, iterables, longest length)."""
+    zoo = {'fundus': Fundus_Multi, 'prostate': Prostate_Multi}
+    if args.gpu_data:
+        from ramdsir import gpu_data
+        zoo = gpu_data.PARAMS
+    transform = {'fundus': Compose([trans.Resize((256, 256)), trans.RandomScaleCrop((256, 256))]), 'prostate': None}
+    loaders, max_len, max_id = [], -1, 0
+    raw, samplers = [], []
+    for idx, i in enumerate(domain_idx_list):
+        ds = zoo[args.dataset](base_dir=data_root, split='train', domain_idx_list=[i], transform=transform[args.dataset],
+                               is_out_domain=args.is_out_domain, test_domain_idx=args.test_domain_idx)
+        # Data parallel (one process per GPU): every domain's list is SHARDED over the ranks (DistributedSampler, reshuffled
+        # per epoch with seed + epoch), each rank draws the reference's per-domain batch sizes from its shard, so one step
+        # consumes world x the reference's batch and an epoch is 1/world as many iterations; RAM partners / lambda / crops
+        # are drawn rank-locally (workers are seeded from seed + rank).  Single process: exactly the reference's loaders.
+        sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed, drop_last=True) if world > 1 else None
+        # the reference's loader settings (train.py:558-559) + persistent workers with a deeper queue: the reference respawns its
+        # 3 x 8 worker processes at every epoch, which costs seconds per 53-iteration epoch -- invisible next to its step time,
+        # 20x the step time here (profiles/README.md, end-to-end throughput)
+        extra = dict(persistent_workers=True, prefetch_factor=4) if args.num_workers > 0 else {}
+        if args.gpu_data:               # the parameter datasets (--gpu_data): draws in this process, records as they are
+            extra = dict(num_workers=0, pin_memory=False, collate_fn=gpu_data.collate)
+        else:
+            extra.update(num_workers=args.num_workers, pin_memory=True)
+        dl = DataLoader(ds, batch_size=bsl[idx], shuffle=sampler is None, sampler=sampler, drop_last=True,
+                        worker_init_fn=seed_worker, **extra)
+        raw.append(dl)
+        samplers.append(sampler)
+        loaders.append(cycle(dl))                       # train.py:560: replays the first pass of the shorter loaders
+        if max_len < len(dl):
+            max_len, max_id = len(dl), idx
+    loaders[max_id] = raw[max_id]
+    return raw, samplers, loaders, max_len
+
+
 def main(args):
     if not (args.ram and args.rec):
         # SURVEY.md F5: the reference only runs end-to-end with --ram --rec (train.py:591 / :315 raise otherwise)
@@ -197,6 +237,7 @@ def main(args):
     # DataLoader workers per domain loader: the reference's 8 (train.py:558) on one GPU; under torchrun every rank has its own
     # three loaders, so the host's cores are divided among ranks x domains (8 ranks x 3 x 8 = 192 decoder processes otherwise)
     n_dom = len(args.domain_idxs.split(','))
+    preload_workers = max(1, worker_cap(args.num_workers, world, 1))     # --gpu_data: threads decoding the resident data (<= 16)
     args.num_workers = worker_cap(args.num_workers, world, n_dom)
     torch.cuda.set_device(local)
     if world > 1 and not dist.is_initialized():
@@ -206,32 +247,18 @@ def main(args):
     host_group = dist.new_group(backend='gloo') if world > 1 else None
     os.makedirs(args.save_path, exist_ok=True)
 
-    zoo = {'fundus': Fundus_Multi, 'prostate': Prostate_Multi}
-    transform = {'fundus': Compose([trans.Resize((256, 256)), trans.RandomScaleCrop((256, 256))]), 'prostate': None}
     bsl = fundus_batch_list[args.test_domain_idx] if args.dataset == 'fundus' else prostate_batch_list[args.test_domain_idx]
     domain_idx_list = [int(i) for i in args.domain_idxs.split(',')]
-    loaders, max_len, max_id = [], -1, 0
-    raw, samplers = [], []
-    for idx, i in enumerate(domain_idx_list):
-        ds = zoo[args.dataset](base_dir=data_root, split='train', domain_idx_list=[i], transform=transform[args.dataset],
-                               is_out_domain=args.is_out_domain, test_domain_idx=args.test_domain_idx)
-        # Data parallel (one process per GPU): every domain's list is SHARDED over the ranks (DistributedSampler, reshuffled
-        # per epoch with seed + epoch), each rank draws the reference's per-domain batch sizes from its shard, so one step
-        # consumes world x the reference's batch and an epoch is 1/world as many iterations; RAM partners / lambda / crops
-        # are drawn rank-locally (workers are seeded from seed + rank).  Single process: exactly the reference's loaders.
-        sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed, drop_last=True) if world > 1 else None
-        # the reference's loader settings (train.py:558-559) + persistent workers with a deeper queue: the reference respawns its
-        # 3 x 8 worker processes at every epoch, which costs seconds per 53-iteration epoch -- invisible next to its step time,
-        # 20x the step time here (profiles/README.md, end-to-end throughput)
-        extra = dict(persistent_workers=True, prefetch_factor=4) if args.num_workers > 0 else {}
-        dl = DataLoader(ds, batch_size=bsl[idx], num_workers=args.num_workers, shuffle=sampler is None, sampler=sampler, drop_last=True,
-                        pin_memory=True, worker_init_fn=seed_worker, **extra)
-        raw.append(dl)
-        samplers.append(sampler)
-        loaders.append(cycle(dl))                       # train.py:560: replays the first pass of the shorter loaders
-        if max_len < len(dl):
-            max_len, max_id = len(dl), idx
-    loaders[max_id] = raw[max_id]
+    raw, samplers, loaders, max_len = make_loaders(args, data_root, world, rank, bsl, domain_idx_list)
+    resident = None
+    if args.gpu_data:
+        # decode once, keep the pixels on this GPU (ramdsir/gpu_data.py); the loaders above only draw
+        from ramdsir import gpu_data
+        t0 = time.time()
+        resident = gpu_data.preload(args.dataset, [dl.dataset for dl in raw], workers=preload_workers)
+        if rank == 0:
+            print('gpu_data: %.2f GB resident, preloaded in %.1f s with %d threads' % (resident.nbytes / 1e9, time.time() - t0,
+                                                                                       preload_workers))
 
     encoder = Encoder(c=args.in_channels, norm=args.norm, activation=args.activation).cuda()
     seg_decoder = Decoder(num_classes=args.num_classes, norm=args.norm, activation=args.activation).cuda()
@@ -243,7 +270,7 @@ def main(args):
 
     from ramdsir.trainer import FusedTrainer, ModuleTrainer
     sample = next(iter(raw[0]))
-    H, W = sample[0].shape[1:3]
+    H, W = resident.hw if resident is not None else sample[0].shape[1:3]
     total_iters = max_len * args.epochs
     cons = args.consistency_type if args.consistency else None
     assert cons in (None, 'mse', 'kd'), args.consistency_type
@@ -270,6 +297,8 @@ def main(args):
             if sp is not None:
                 sp.set_epoch(epoch)
         def on_device(batches):
+            if resident is not None:                    # --gpu_data: one rd_fundus_batch / rd_prostate_batch launch
+                return resident.on_device(batches)
             return tuple(torch.cat([b[k] for b in batches], 0).cuda(non_blocking=True) for k in range(4))       # src, trg, lam, mask
 
         # one batch of look-ahead: the step of batch i also mixes batch i+1 (RAM) in its tail, beside Adam and the weight repack
