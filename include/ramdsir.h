@@ -546,6 +546,35 @@ typedef struct {
 } rd_prostate_batch_t;
 int rd_prostate_batch(const rd_prostate_batch_t* p, const rd_prostate_sample_t* samples_host, int B, void* stream);
 
+/* In-training Fundus validation after the forward pass (train.py --gpu_val; code/train.py:91-132, code/utils/utils.py:19-28,45-96),
+ * csrc/val_post.hip.  Images have their own native sizes; each owns two planes (0 cup, 1 disc) of h x w bytes, stored back to back.
+ * All three take B HOST records (read before the call returns: they travel as kernel arguments, RD_VAL_CHUNK per launch), launch on
+ * `stream`, never synchronise and return -1 for an invalid record or a buffer too small for it.
+ *   rd_val_threshold  mask = F.interpolate(sigmoid(logits), (h, w), mode='bilinear', align_corners=False) > 0.75 as 0 / 1 bytes at
+ *                     mask + off, for image b of logits fp32 [B][2][Sh][Sw] (contiguous NCHW).  fp32 throughout: scale = (float)S / out,
+ *                     src = max(scale * (dst + 0.5f) - 0.5f, 0), i0 = (int)src, i1 = min(i0 + 1, S - 1), weight src - i0, the horizontal
+ *                     pairs first, then the vertical one, every operation rounded on its own (ramdsir/gpu_val.py resize_threshold_model).
+ *   rd_val_post       per plane: keep the largest 8-connected component of mask (ties: the one whose first pixel in raster order comes
+ *                     first; an empty plane stays empty), then turn every background pixel that is not 4-connected to the image border
+ *                     into foreground -> post (bit-identical to utils.metrics.postprocess_binary; ramdsir/gpu_val.py postprocess_model).
+ *                     mask and post are distinct buffers with the same layout.  With gt (0 / non-0 bytes, the image's planes at gt_off)
+ *                     and counts (int32 [n_slots][2][3], zeroed by the caller before a pass) it adds |post|, |gt|, |post & gt| of every
+ *                     plane to counts[slot][plane]; gt and counts are given together or both NULL.  Integer atomics only: the result does
+ *                     not depend on scheduling.  workspace: rd_val_post_workspace(images, B) bytes, 16-byte aligned, contents irrelevant. */
+typedef struct {
+    int64_t off;                /* byte offset of the image's (2, h, w) planes in mask and post */
+    int64_t gt_off;             /* byte offset of its (2, h, w) target planes in gt */
+    int32_t h, w;
+    int32_t slot;               /* row of counts the image adds to */
+    int32_t pad_;
+} rd_val_image_t;
+#define RD_VAL_CHUNK 32
+int rd_val_threshold(const float* logits, int B, int Sh, int Sw, const rd_val_image_t* images_host, uint8_t* mask, int64_t mask_bytes,
+                     void* stream);
+int64_t rd_val_post_workspace(const rd_val_image_t* images_host, int B);
+int rd_val_post(const uint8_t* mask, uint8_t* post, int64_t mask_bytes, const uint8_t* gt, int64_t gt_bytes, int32_t* counts, int n_slots,
+                void* workspace, int64_t workspace_bytes, const rd_val_image_t* images_host, int B, void* stream);
+
 /* Measurement only (bench.py `box`): what this box's GPU sustains on two fixed micro-kernels, so that a bench line can be compared across
  * boxes of a pool whose clocks differ by a few per cent.  No reference counterpart (the reference publishes no throughput: BASELINE.md).
  *   which 0: streaming copy of n bytes (n % 16 == 0) from a to b, 16 B per lane, 8 workgroups of 256 threads per CU;

@@ -106,6 +106,13 @@ class RdProstateBatch(C.Structure):
     _fields_ = [('slices', fp), ('masks', vp), ('src', fp), ('trg', fp), ('lam', fp), ('mask', vp), ('n_slices', i32), ('S', i32)]
 
 
+VAL_CHUNK = 32         # RD_VAL_CHUNK
+
+
+class RdValImage(C.Structure):
+    _fields_ = [('off', i64), ('gt_off', i64), ('h', i32), ('w', i32), ('slot', i32), ('pad_', i32)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -172,6 +179,9 @@ _SIGS = {
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),
     'rd_prostate_batch': (C.c_int, [C.POINTER(RdProstateBatch), C.POINTER(RdProstateSample), C.c_int, vp]),
+    'rd_val_threshold': (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.POINTER(RdValImage), vp, i64, vp]),
+    'rd_val_post_workspace': (i64, [C.POINTER(RdValImage), C.c_int]),
+    'rd_val_post': (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, vp, i64, C.POINTER(RdValImage), C.c_int, vp]),
 }
 
 _lib = None

@@ -86,6 +86,10 @@ def parse_args(argv=None):
     p.add_argument('--gpu_data', action='store_true',
                    help='decode the training images once and keep them in device memory; the augmentation runs as one HIP launch per '
                         'step (bit-identical to the host path with --num_workers 0, which then only sizes the preload thread pool)')
+    p.add_argument('--gpu_val', action='store_true',
+                   help='fundus: keep the held-out test set in device memory and run everything after the validation forward pass '
+                        '(resize, threshold, largest component + hole filling, Dice counts) as HIP kernels; the reported numbers are '
+                        'those of the host path')
     return p.parse_args(argv)
 
 
@@ -163,6 +167,36 @@ def test_fundus(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path,
     return (cup + disc) * 100.0 / 2
 
 
+def _val_testset(data_dir, datasetTest):
+    return Fundus(base_dir=data_dir, split='test', domain_idx=datasetTest, transform=Compose([trans.Resize((256, 256)), trans.Normalize()]))
+
+
+_VAL_GPU = {}
+
+
+def test_fundus_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='fundus'):
+    """test_fundus with everything after the forward pass on the GPU (--gpu_val; ramdsir/gpu_val.py, csrc/val_post.hip): the same
+    batches in list order through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.
+    The resident test set is main()'s preload (or is made here at the first call)."""
+    from ramdsir import gpu_val
+    key = (data_dir, datasetTest)
+    if key not in _VAL_GPU:
+        _VAL_GPU[key] = gpu_val.preload(_val_testset(data_dir, datasetTest), batch_size=batch_size)
+        if _VAL_GPU[key] is None:
+            raise RuntimeError('--gpu_val: the test set does not fit in device memory')
+    dices = gpu_val.validate(encoder, seg_decoder, _VAL_GPU[key], batch_size)
+    cup = disc = 0.0
+    n = 0
+    for c, d in dices:
+        cup, disc, n = cup + c, disc + d, n + 1
+    cup, disc = cup / max(n, 1), disc / max(n, 1)
+    print('val_cup_dice : {}, val_disc_dice : {}'.format(cup, disc))
+    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
+        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['cup dice coefficence: '] + [cup] +
+                                   ['disc dice coefficence: '] + [disc]])) + '\n')
+    return (cup + disc) * 100.0 / 2
+
+
 def test_prostate(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='prostate'):
     """train.py:134-192: Dice over the NIfTI volumes of the held-out site (BN in eval mode), one line in
     <target>_val_log.csv.  `data_dir` is the dataset directory (<data_root>/prostate)."""
@@ -224,6 +258,8 @@ def main(args):
     if not (args.ram and args.rec):
         # the reference only runs end-to-end with --ram --rec (train.py:591 / :315 raise otherwise)
         raise ValueError('only the --ram --rec flag combination exists in the reference; got ram=%s rec=%s' % (args.ram, args.rec))
+    if args.gpu_val and args.dataset != 'fundus':
+        raise ValueError('--gpu_val covers the in-training Fundus validation only; --dataset %s validates on the host' % args.dataset)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -232,7 +268,12 @@ def main(args):
     # HERE, before the first GPU call of this process: their children are forked from an address space that has never initialised
     # HIP (rank 0 validates, below)
     has_val = args.dataset == 'fundus' and os.path.exists(os.path.join(data_root, 'Domain%d_test.list' % (args.test_domain_idx + 1)))
-    if rank == 0 and has_val:
+    if rank == 0 and has_val and args.gpu_val:
+        # The host path starts its test loader's iterator at this point (_val_resources), and a DataLoader iterator takes one 64-bit
+        # draw from torch's global generator for its base seed -- the generator the training samplers shuffle from.  --gpu_val creates
+        # neither the loader nor the pool; it takes that one draw here, so that the trained model does not depend on the flag.
+        torch.empty((), dtype=torch.int64).random_()
+    elif rank == 0 and has_val:
         _val_resources(data_root, args.test_domain_idx, args.test_batch_size)
     # DataLoader workers per domain loader: the reference's 8 (train.py:558) on one GPU; under torchrun every rank has its own
     # three loaders, so the host's cores are divided among ranks x domains (8 ranks x 3 x 8 = 192 decoder processes otherwise)
@@ -259,6 +300,21 @@ def main(args):
         if rank == 0:
             print('gpu_data: %.2f GB resident, preloaded in %.1f s with %d threads' % (resident.nbytes / 1e9, time.time() - t0,
                                                                                        preload_workers))
+
+    validate = test_fundus
+    if rank == 0 and has_val and args.gpu_val:
+        # the held-out test set, decoded once and kept on this GPU (ramdsir/gpu_val.py); the host path if it does not fit
+        from ramdsir import gpu_val
+        t0 = time.time()
+        val_set = gpu_val.preload(_val_testset(data_root, args.test_domain_idx), workers=preload_workers, batch_size=args.test_batch_size)
+        if val_set is not None:
+            _VAL_GPU[(data_root, args.test_domain_idx)] = val_set
+            validate = test_fundus_gpu
+            print('gpu_val: %d test images, %.3f GB resident, preloaded in %.1f s' % (len(val_set), val_set.nbytes / 1e9, time.time() - t0))
+        else:
+            rng_state = torch.get_rng_state()               # the loader's draw has been taken above
+            _val_resources(data_root, args.test_domain_idx, args.test_batch_size)
+            torch.set_rng_state(rng_state)
 
     encoder = Encoder(c=args.in_channels, norm=args.norm, activation=args.activation).cuda()
     seg_decoder = Decoder(num_classes=args.num_classes, norm=args.norm, activation=args.activation).cuda()
@@ -342,7 +398,7 @@ def main(args):
         avg_dice = None
         if rank == 0 and args.dataset == 'fundus' and os.path.exists(os.path.join(data_root, 'Domain%d_test.list' % (args.test_domain_idx + 1))):
             print('Test on target domain {}'.format(args.test_domain_idx))
-            avg_dice = test_fundus(encoder, seg_decoder, epoch, data_root, args.test_domain_idx, args.save_path, args.test_batch_size)
+            avg_dice = validate(encoder, seg_decoder, epoch, data_root, args.test_domain_idx, args.save_path, args.test_batch_size)
         elif rank == 0 and args.dataset == 'prostate':
             from utils.prostate_eval import DOMAIN_LIST
             if os.path.isdir(os.path.join(data_root, DOMAIN_LIST[args.test_domain_idx])):
@@ -373,6 +429,7 @@ def main(args):
     if writer is not None:
         writer.close()
     _close_val()
+    _VAL_GPU.clear()
     if world > 1:
         dist.barrier(group=host_group)
 
