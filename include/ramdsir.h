@@ -575,6 +575,38 @@ int64_t rd_val_post_workspace(const rd_val_image_t* images_host, int B);
 int rd_val_post(const uint8_t* mask, uint8_t* post, int64_t mask_bytes, const uint8_t* gt, int64_t gt_bytes, int32_t* counts, int n_slots,
                 void* workspace, int64_t workspace_bytes, const rd_val_image_t* images_host, int B, void* stream);
 
+/* In-training Prostate validation around the forward pass (train.py --gpu_val_volumes; code/train.py:134-192,
+ * code/utils/utils.py:30-42), csrc/val_volume.hip.  A volume is (D, H, W) in raster order; its fp32 voxels, normalised on the host at
+ * preload, stay on the device.  frames_host: B HOST frame indices (read before the call returns: they travel as kernel arguments,
+ * RD_VAL_CHUNK per launch), -1 for an empty slot, otherwise 1 <= jj <= D - 2 and increasing.  All entry points launch on `stream`,
+ * never synchronise and return -1 for an invalid argument or record or a buffer too small for it, before anything is launched.
+ *   rd_vol_stack   the 2.5-D batch of code/train.py:161-168: out fp32 [B][3][H][W] (contiguous), channel c of slot b = slice
+ *                  frames[b] - 1 + c of `volume`; an empty slot is all zeros.  A pure copy.
+ *   rd_vol_argmax  code/train.py:170-176: slice jj = frames[b] of `pred` (0 / 1 bytes, (D, H, W)) := argmax over the two classes of
+ *                  logits fp32 [B][2][H][W] (contiguous NCHW), the first maximum winning (1 iff l1 > l0) -- or zeros where
+ *                  gt_empty[jj] != 0 (D bytes: the slices whose ground truth sums to 0).  Empty slots write nothing; slices that no
+ *                  call reaches keep what the caller cleared them to (rd_zero, once per pass).
+ *   rd_vol_post    code/utils/utils.py:30-42 `_connectivity_region_analysis`: per volume, keep the largest 6-connected (face)
+ *                  component of pred (ties: the one whose first voxel in (z, y, x) raster order comes first); an EMPTY prediction
+ *                  becomes all ones, as the reference's `keep == 0` does -> post (bit-identical to
+ *                  utils.metrics.connectivity_region_analysis; ramdsir/gpu_val_volumes.py largest_component_model).  pred and post are
+ *                  distinct buffers with the same layout.  With gt (0 / non-0 bytes, the volume at gt_off) and counts (int32
+ *                  [n_slots][3], zeroed by the caller before a pass) it adds |post|, |gt|, |post & gt| to counts[slot]; gt and counts
+ *                  are given together or both NULL.  Integer atomics only: the result does not depend on scheduling.
+ *                  workspace: rd_vol_post_workspace(volumes, B) bytes, 16-byte aligned, contents irrelevant. */
+typedef struct {
+    int64_t off;                /* byte offset of the volume's (d, h, w) bytes in pred and post */
+    int64_t gt_off;             /* byte offset of its ground truth in gt */
+    int32_t d, h, w;
+    int32_t slot;               /* row of counts the volume adds to */
+} rd_val_volume_t;
+int rd_vol_stack(const float* volume, int D, int H, int W, const int32_t* frames_host, int B, float* out, void* stream);
+int rd_vol_argmax(const float* logits, int B, int H, int W, const int32_t* frames_host, const uint8_t* gt_empty, int D, uint8_t* pred,
+                  void* stream);
+int64_t rd_vol_post_workspace(const rd_val_volume_t* volumes_host, int B);
+int rd_vol_post(const uint8_t* pred, uint8_t* post, int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int32_t* counts, int n_slots,
+                void* workspace, int64_t workspace_bytes, const rd_val_volume_t* volumes_host, int B, void* stream);
+
 /* Measurement only (bench.py `box`): what this box's GPU sustains on two fixed micro-kernels, so that a bench line can be compared across
  * boxes of a pool whose clocks differ by a few per cent.  No reference counterpart (the reference publishes no throughput: BASELINE.md).
  *   which 0: streaming copy of n bytes (n % 16 == 0) from a to b, 16 B per lane, 8 workgroups of 256 threads per CU;

@@ -8,6 +8,7 @@
 // component is its first pixel in raster order -- which is scipy's component numbering, so "largest area, then smallest root" is
 // argmax's first maximum.  Integer atomics only; no workgroup waits for another: every phase is a launch of its own.
 #include "common.h"
+#include "val_uf.h"
 #include "../../include/ramdsir.h"
 
 namespace {
@@ -73,29 +74,7 @@ __global__ __launch_bounds__(kThreads) void val_threshold_kernel(const float* __
     mask[pl.pix + i] = v > 0.75f ? 1 : 0;
 }
 
-// ---- stage b: union-find ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int load_parent(const int* P, int n) { return __hip_atomic_load(P + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// at most n steps: parent[n] <= n
-__device__ __forceinline__ int find_root(const int* P, int n) {
-    for (int p = load_parent(P, n); p != n; p = load_parent(P, n)) n = p;
-    return n;
-}
-
-// Links the larger root under the smaller with atomicMin.  A retry happens only when another thread has lowered parent[a] in between;
-// its old value is then united with b in turn, so no link is lost, and every retry starts from a strictly smaller node.
-__device__ __forceinline__ void unite(int* P, int a, int b) {
-    for (;;) {
-        a = find_root(P, a);
-        b = find_root(P, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(P + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
+// ---- stage b: union-find (find_root, unite: val_uf.h) -------------------------------------------------------------------------------
 // BG = false: the foreground of `img` (8-connectivity); BG = true: its background (4-connectivity + the border node)
 template <bool BG>
 __device__ __forceinline__ bool member(const uint8_t* img, int i) { return (img[i] != 0) != BG; }

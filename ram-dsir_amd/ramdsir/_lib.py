@@ -113,6 +113,10 @@ class RdValImage(C.Structure):
     _fields_ = [('off', i64), ('gt_off', i64), ('h', i32), ('w', i32), ('slot', i32), ('pad_', i32)]
 
 
+class RdValVolume(C.Structure):
+    _fields_ = [('off', i64), ('gt_off', i64), ('d', i32), ('h', i32), ('w', i32), ('slot', i32)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -182,6 +186,10 @@ _SIGS = {
     'rd_val_threshold': (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.POINTER(RdValImage), vp, i64, vp]),
     'rd_val_post_workspace': (i64, [C.POINTER(RdValImage), C.c_int]),
     'rd_val_post': (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, vp, i64, C.POINTER(RdValImage), C.c_int, vp]),
+    'rd_vol_stack': (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.POINTER(i32), C.c_int, fp, vp]),
+    'rd_vol_argmax': (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.POINTER(i32), vp, C.c_int, vp, vp]),
+    'rd_vol_post_workspace': (i64, [C.POINTER(RdValVolume), C.c_int]),
+    'rd_vol_post': (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, vp, i64, C.POINTER(RdValVolume), C.c_int, vp]),
 }
 
 _lib = None

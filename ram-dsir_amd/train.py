@@ -90,6 +90,9 @@ def parse_args(argv=None):
                    help='fundus: keep the held-out test set in device memory and run everything after the validation forward pass '
                         '(resize, threshold, largest component + hole filling, Dice counts) as HIP kernels; the reported numbers are '
                         'those of the host path')
+    p.add_argument('--gpu_val_volumes', action='store_true',
+                   help='prostate: keep the held-out site\'s volumes in device memory and build the 2.5-D batches, take the argmax, keep '
+                        'the largest 3-D component and count for the Dice as HIP kernels; the reported numbers are those of the host path')
     return p.parse_args(argv)
 
 
@@ -211,6 +214,30 @@ def test_prostate(encoder, seg_decoder, epoch, data_dir, datasetTest, output_pat
     return val_dice * 100.0
 
 
+_VAL_VOL = {}
+
+
+def test_prostate_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='prostate'):
+    """test_prostate on the resident volumes (--gpu_val_volumes; ramdsir/gpu_val_volumes.py, csrc/val_volume.hip): the same batches
+    through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.  The resident
+    volumes are main()'s preload (or are made here at the first call)."""
+    from ramdsir import gpu_val_volumes
+    from utils.prostate_eval import DOMAIN_LIST
+    key = (data_dir, datasetTest)
+    if key not in _VAL_VOL:
+        _VAL_VOL[key] = gpu_val_volumes.preload(data_dir, DOMAIN_LIST[datasetTest], batch_size=batch_size)
+        if _VAL_VOL[key] is None:
+            raise RuntimeError('--gpu_val_volumes: the volumes do not fit in device memory')
+    val_dice = 0.0
+    for d in gpu_val_volumes.validate(encoder, seg_decoder, _VAL_VOL[key], batch_size):
+        val_dice += d
+    val_dice = val_dice / max(len(_VAL_VOL[key]), 1)
+    print('val_dice : {}'.format(val_dice))
+    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
+        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['dice coefficence: '] + [val_dice]])) + '\n')
+    return val_dice * 100.0
+
+
 def save_checkpoint(path, encoder, seg_decoder, rec_decoder):
     """train.py:342-360: unwrapped state_dicts under the reference's three keys."""
     torch.save({'encoder_state_dict': encoder.state_dict(), 'seg_decoder_state_dict': seg_decoder.state_dict(),
@@ -260,6 +287,8 @@ def main(args):
         raise ValueError('only the --ram --rec flag combination exists in the reference; got ram=%s rec=%s' % (args.ram, args.rec))
     if args.gpu_val and args.dataset != 'fundus':
         raise ValueError('--gpu_val covers the in-training Fundus validation only; --dataset %s validates on the host' % args.dataset)
+    if args.gpu_val_volumes and args.dataset != 'prostate':
+        raise ValueError('--gpu_val_volumes covers the in-training Prostate validation only; --dataset %s has --gpu_val' % args.dataset)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -315,6 +344,24 @@ def main(args):
             rng_state = torch.get_rng_state()               # the loader's draw has been taken above
             _val_resources(data_root, args.test_domain_idx, args.test_batch_size)
             torch.set_rng_state(rng_state)
+
+    validate_prostate = test_prostate
+    if rank == 0 and args.gpu_val_volumes and args.num_classes != 2:
+        # the host path sums the class indices of a component (ndi.sum(mask, ...)); the kernels count voxels: two classes only
+        print('gpu_val_volumes: --num_classes %d is not 2: validating on the host' % args.num_classes)
+    elif rank == 0 and args.gpu_val_volumes:
+        # the held-out site's volumes, read once and kept on this GPU (ramdsir/gpu_val_volumes.py); the host path if they do not fit.
+        # The host path creates no loader for Prostate, so there is no random draw to reproduce here.
+        from ramdsir import gpu_val_volumes
+        from utils.prostate_eval import DOMAIN_LIST
+        if os.path.isdir(os.path.join(data_root, DOMAIN_LIST[args.test_domain_idx])):
+            t0 = time.time()
+            vols = gpu_val_volumes.preload(data_root, DOMAIN_LIST[args.test_domain_idx], batch_size=args.test_batch_size, workers=preload_workers)
+            if vols is not None:
+                _VAL_VOL[(data_root, args.test_domain_idx)] = vols
+                validate_prostate = test_prostate_gpu
+                print('gpu_val_volumes: %d volumes, %.3f GB resident + %.3f GB scratch, preloaded in %.1f s'
+                      % (len(vols), vols.nbytes / 1e9, vols.scratch_bytes / 1e9, time.time() - t0))
 
     encoder = Encoder(c=args.in_channels, norm=args.norm, activation=args.activation).cuda()
     seg_decoder = Decoder(num_classes=args.num_classes, norm=args.norm, activation=args.activation).cuda()
@@ -403,7 +450,7 @@ def main(args):
             from utils.prostate_eval import DOMAIN_LIST
             if os.path.isdir(os.path.join(data_root, DOMAIN_LIST[args.test_domain_idx])):
                 print('Test on target domain {}'.format(args.test_domain_idx))
-                avg_dice = test_prostate(encoder, seg_decoder, epoch, data_root, args.test_domain_idx, args.save_path, args.test_batch_size)
+                avg_dice = validate_prostate(encoder, seg_decoder, epoch, data_root, args.test_domain_idx, args.save_path, args.test_batch_size)
         if world > 1:
             # every rank has finished its epoch (synchronize above) and none has entered the next step's all-reduce: the
             # other ranks wait HERE, on the host (gloo), while rank 0 validates with replica 0's BatchNorm statistics (what
@@ -430,6 +477,7 @@ def main(args):
         writer.close()
     _close_val()
     _VAL_GPU.clear()
+    _VAL_VOL.clear()
     if world > 1:
         dist.barrier(group=host_group)
 

@@ -24,17 +24,29 @@ def load_case(data_dir, domain_name, file_name):
     return image, mask
 
 
+def normalise_volume(image):
+    """Per-volume min-max normalisation to [-1, 1] (code/train.py:153-155) in whatever dtype read_volume returned: the one
+    expression both the host path (predict_volume) and the resident path (ramdsir/gpu_val_volumes.py preload) feed from."""
+    image = np.asarray(image)
+    mx, mn = np.max(image), np.min(image)
+    return 2 * (image - mn) / (mx - mn) - 1
+
+
+def merge_labels(mask):
+    """A copy of the ground truth with label 2 folded into 1 (code/train.py:157)."""
+    mask = np.array(mask)
+    mask[mask == 2] = 1
+    return mask
+
+
 def predict_volume(forward, image, mask, batch_size):
     """forward: (B,3,H,W) float32 tensor -> (B,K,H,W) logits.  Mirrors the reference loop exactly, including what
     reads like slips and therefore shapes the numbers: only floor(D / batch_size) batches run, so frames beyond
     that many batches are never predicted (test_prostate_volume.py:103); a batch is always `batch_size` wide, the
     slots beyond the frame list stay all-zero images and still take part in the batch statistics of a train-mode
     BatchNorm (:104-108); slices with an empty ground truth keep a zero prediction (:113-116)."""
-    image = np.asarray(image)
-    mx, mn = np.max(image), np.min(image)
-    image = 2 * (image - mn) / (mx - mn) - 1
-    mask = np.array(mask)
-    mask[mask == 2] = 1
+    image = normalise_volume(image)
+    mask = merge_labels(mask)
     pred_y = np.zeros(mask.shape)
     frame_list = list(range(1, image.shape[0] - 1))
     for ii in range(int(np.floor(image.shape[0] // batch_size))):
