@@ -981,8 +981,9 @@ def test_conv_kernels_under_forced_dispatch(env):
     import sys
     e = dict(os.environ, RAMDSIR_DEBUG_LIB='1')        # the RD_* overrides exist only in the debug build (csrc/common.h rd_switch)
     e.update(env)
-    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-m', 'gpu', '-k',
-                        'test_conv_forward or test_conv_gradient_epilogues or test_conv_bnbwd'], env=e,
+    here = os.path.abspath(__file__)
+    r = subprocess.run([sys.executable, '-m', 'pytest', here, os.path.join(os.path.dirname(here), 'test_gpu_exact.py'), '-q', '-x', '-m', 'gpu', '-k',
+                        'test_conv_forward or test_conv_gradient_epilogues or test_conv_bnbwd or test_exact_conv'], env=e,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     tail = r.stdout.decode()[-2500:]
     assert r.returncode == 0, tail
