@@ -162,6 +162,13 @@ typedef struct {
 
 int64_t rd_wgrad_workspace(const rd_wgrad_t* p, int dtype);
 int rd_wgrad(const rd_wgrad_t* p, int dtype, void* stream);
+/* The split reduction that ends rd_wgrad and rd_conv_bwd_fused_reduce, on its own: dW[n][c][tap] = (beta ? beta * dW : 0) +
+ * the sum over s < nsplit of partial[s][tap][n < CoutPadW][c < CinPadW], fp32, in a fixed order that does not depend on the load
+ * width the launch picks.  CinPadW is a multiple of 16 (else -1).  16-byte loads are used when Cin % 4 == 0, `partial` is
+ * 16-byte aligned and the launch has 8 split lanes per output (fewer than 128 splits, or more than 16384 outputs); in every other
+ * case, a misaligned `partial` included, the 4-byte form runs without notice -- same bits.  dW is read only when beta != 0. */
+int rd_wgrad_reduce(const float* partial, float* dW, int nsplit, int taps, int Cout, int Cin, int CoutPadW, int CinPadW, float beta,
+                    void* stream);
 
 /* Backward of a small-channel 3x3 conv (<= 32 channels in and out, bf16, plain per-pixel sources and destinations: every
  * 400x400 / 200x200 layer of the U-Net) in ONE launch: cudnn's dgrad AND wgrad behind the same nn.Conv2d

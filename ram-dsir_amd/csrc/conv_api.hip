@@ -149,6 +149,12 @@ int rd_wgrad(const rd_wgrad_t* p, int dtype, void* stream) {
     return rd_wgrad_dispatch(*p, dtype, (hipStream_t)stream);
 }
 
+int rd_wgrad_reduce(const float* partial, float* dW, int nsplit, int taps, int Cout, int Cin, int CoutPadW, int CinPadW, float beta,
+                    void* stream) {
+    if (!partial || !dW || nsplit < 1 || taps < 1 || Cout < 1 || Cin < 1 || CoutPadW < Cout || CinPadW < Cin || CinPadW % 16) return -1;
+    return rd_wgrad_reduce_launch(partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta, (hipStream_t)stream);
+}
+
 // ---- backward of a small-channel 3x3 conv in one launch (conv_fused.hip)
 int rd_conv_bwd_fused_ok(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype) {
     if (!dgrad || !wgrad || dgrad->G < 1 || dgrad->G > RD_MAX_GROUPS) return 0;

@@ -825,13 +825,16 @@ __global__ __launch_bounds__(256, 3) void wgrad_c16_tr_kernel(const rd_wgrad_t p
     }
 }
 
-// Split reduction.  (A float4-coalesced, chunked variant with atomics into a zeroed dW measured 320 us/step SLOWER over
-// the 40 launches -- the extra memset launch and fewer blocks in flight cost more than the strided reads, which are L2 hits
-// on partials written microseconds earlier: profiles/README.md round 2.)
-// block = 32 outputs x 8 split lanes: each thread sums every 8th split, LDS folds the 8 lanes in a fixed order
+// Split reduction: wgrad_reduce_kernel<OB, V> at the end of this block, in two forms that follow -- the scalar one (V = 1) and the
+// 16-byte-load one (V = 4).  QL = 256 / OB split lanes share one output's splits: lane ql sums splits ql, ql + QL, ..., LDS folds the
+// lanes in a fixed order.  OB = 32 (8 split lanes) unless there are many splits of a small filter, then OB = 8 (32 lanes):
+// rd_wgrad_reduce_launch.  (A float4-coalesced, chunked variant with ATOMICS into a zeroed dW measured 320 us/step SLOWER over the 40
+// launches -- the extra memset launch and fewer blocks in flight cost more than the strided reads, which are L2 hits on partials
+// written microseconds earlier: profiles/README.md round 2.)
+// scalar form: block = OB outputs x QL split lanes
 template <int OB>                                         // outputs per block; 256/OB threads share one output's splits
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* partial, float* dW, int nsplit, int taps, int Cout,
-                                                           int Cin, int CoutPadW, int CinPadW, float beta) {
+__device__ __forceinline__ void wgrad_reduce_scalar(const float* partial, float* dW, int nsplit, int taps, int Cout,
+                                                    int Cin, int CoutPadW, int CinPadW, float beta) {
     constexpr int QL = 256 / OB;
     __shared__ float s[QL][OB];
     const int total = taps * Cout * Cin;
@@ -866,6 +869,70 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* partial,
         }
         __syncthreads();
     }
+}
+
+// The same tree with 16-byte loads (Cin % 4 == 0; CinPadW is a multiple of 16, so four consecutive outputs along c are one aligned
+// float4 of every split): a thread owns 4 outputs of one (tap, n) and keeps four float4 loads in flight where the scalar kernel keeps
+// four dwords.  Every output's sum is the scalar kernel's, operation for operation -- split lane ql adds splits ql, ql + QL, ... round-robin
+// into a0..a3, the remainder into a0, (a0 + a1) + (a2 + a3), the LDS fold over q ascending from 0 -- so dW is bit-identical.  The fold is
+// spread over 4 * OB threads (one per output) instead of OB.
+template <int OB>                                         // float4 columns per block (4 * OB outputs); 256/OB split lanes as above
+__device__ __forceinline__ void wgrad_reduce_vec4(const float* partial, float* dW, int nsplit, int taps, int Cout,
+                                                  int Cin, int CoutPadW, int CinPadW, float beta) {
+    constexpr int QL = 256 / OB;
+    __shared__ __align__(16) float s[QL][OB * 4];         // written as float4
+    const int total = taps * Cout * Cin;                   // a multiple of 4
+    const int o = threadIdx.x % OB, ql = threadIdx.x / OB;
+    const size_t stride = (size_t)taps * CoutPadW * CinPadW;
+    for (int base = blockIdx.x * (OB * 4); base < total; base += gridDim.x * (OB * 4)) {
+        const int i = base + 4 * o;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < total) {
+            const int c = i % Cin, n = (i / Cin) % Cout, tap = i / (Cin * Cout);
+            const float* src = partial + ((size_t)tap * CoutPadW + n) * CinPadW + c;
+            float4 a0 = acc, a1 = acc, a2 = acc, a3 = acc;
+            int k = ql;
+            for (; k + 3 * QL < nsplit; k += 4 * QL) {
+                const float4 v0 = *reinterpret_cast<const float4*>(src + (size_t)k * stride);
+                const float4 v1 = *reinterpret_cast<const float4*>(src + (size_t)(k + QL) * stride);
+                const float4 v2 = *reinterpret_cast<const float4*>(src + (size_t)(k + 2 * QL) * stride);
+                const float4 v3 = *reinterpret_cast<const float4*>(src + (size_t)(k + 3 * QL) * stride);
+                a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
+                a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
+                a2.x += v2.x; a2.y += v2.y; a2.z += v2.z; a2.w += v2.w;
+                a3.x += v3.x; a3.y += v3.y; a3.z += v3.z; a3.w += v3.w;
+            }
+            for (; k < nsplit; k += QL) {
+                const float4 v0 = *reinterpret_cast<const float4*>(src + (size_t)k * stride);
+                a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
+            }
+            acc.x = (a0.x + a1.x) + (a2.x + a3.x);
+            acc.y = (a0.y + a1.y) + (a2.y + a3.y);
+            acc.z = (a0.z + a1.z) + (a2.z + a3.z);
+            acc.w = (a0.w + a1.w) + (a2.w + a3.w);
+        }
+        *reinterpret_cast<float4*>(&s[ql][4 * o]) = acc;
+        __syncthreads();
+        const int j = base + (int)threadIdx.x;             // thread t < 4 * OB folds output base + t
+        if (threadIdx.x < OB * 4 && j < total) {
+            float v = 0.f;
+#pragma unroll
+            for (int q = 0; q < QL; ++q) v += s[q][threadIdx.x];
+            const int c = j % Cin, n = (j / Cin) % Cout, tap = j / (Cin * Cout);
+            float* d = dW + ((size_t)n * Cin + c) * taps + tap;
+            *d = (beta != 0.f ? beta * *d : 0.f) + v;
+        }
+        __syncthreads();
+    }
+}
+
+// The kernel: OB output columns x 256 / OB split lanes per block; V = 4: the float4 form (Cin % 4 == 0, 16-byte-aligned partials: a
+// block covers 4 * OB outputs), V = 1: the scalar form.  Both give the same bits (tests/test_gpu_wgrad_reduce.py).
+template <int OB, int V>
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* partial, float* dW, int nsplit, int taps, int Cout,
+                                                           int Cin, int CoutPadW, int CinPadW, float beta) {
+    if constexpr (V == 4) wgrad_reduce_vec4<OB>(partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
+    else wgrad_reduce_scalar<OB>(partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
 }
 
 // every source a plain per-pixel read (no pooling / on-the-fly upsampling) of whole 16-byte channel slots
@@ -1071,13 +1138,18 @@ int dispatch_wgrad(const rd_wgrad_t& p, hipStream_t st) {
 int rd_wgrad_reduce_launch(const float* partial, float* dW, int nsplit, int taps, int Cout, int Cin, int CoutPadW, int CinPadW, float beta,
                            hipStream_t st) {
     const int total = taps * Cout * Cin;
-    // many splits of a small filter (the 16/32-channel layers): 8 outputs x 32 split lanes per block
+    // many splits of a small filter (the 16/32-channel layers): 8 outputs x 32 split lanes per block, scalar loads -- 32 loads per output
+    // are in flight there already, and four outputs per thread would leave a quarter of the blocks (measured: 10.7 -> 13.2 us)
     if (nsplit >= 128 && total <= 16384) {
-        rd_launch(wgrad_reduce_kernel<8>, dim3((total + 7) / 8), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
+        rd_launch((wgrad_reduce_kernel<8, 1>), dim3((total + 7) / 8), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
     } else {
-        int blocks = (total + 31) / 32;
+        // 8 split lanes: a thread has one or two loads in flight with few splits -> whole float4 columns when Cin % 4 == 0 (CinPadW, hence
+        // every row and split of the partials, is a multiple of 16 floats).  RD_WG_REDUCE_V4=0 (debug library): the scalar form everywhere
+        const bool v4 = Cin % 4 == 0 && (((uintptr_t)partial) & 15) == 0 && rd_switch("RD_WG_REDUCE_V4", 1);
+        int blocks = v4 ? (total + 127) / 128 : (total + 31) / 32;
         if (blocks > 8192) blocks = 8192;
-        rd_launch(wgrad_reduce_kernel<32>, dim3(blocks), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
+        if (v4) rd_launch((wgrad_reduce_kernel<32, 4>), dim3(blocks), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
+        else rd_launch((wgrad_reduce_kernel<32, 1>), dim3(blocks), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
     }
     return (int)hipGetLastError();
 }

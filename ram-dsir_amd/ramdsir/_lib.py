@@ -143,6 +143,7 @@ _SIGS = {
     'rd_conv': (C.c_int, [C.POINTER(RdConv), C.c_int, vp]),
     'rd_wgrad_workspace': (i64, [C.POINTER(RdWgrad), C.c_int]),
     'rd_wgrad': (C.c_int, [C.POINTER(RdWgrad), C.c_int, vp]),
+    'rd_wgrad_reduce': (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
     'rd_conv_honours_src_out': (C.c_int, [C.POINTER(RdConv), C.c_int]),
     'rd_conv_bwd_fused_ok': (C.c_int, [C.POINTER(RdConv), C.POINTER(RdWgrad), C.c_int]),
     'rd_conv_bwd_fused_workspace': (i64, [C.POINTER(RdConv), C.POINTER(RdWgrad), C.c_int]),
