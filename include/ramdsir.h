@@ -19,6 +19,7 @@
  */
 #ifndef RAMDSIR_H
 #define RAMDSIR_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -613,6 +614,56 @@ int rd_vol_argmax(const float* logits, int B, int H, int W, const int32_t* frame
 int64_t rd_vol_post_workspace(const rd_val_volume_t* volumes_host, int B);
 int rd_vol_post(const uint8_t* pred, uint8_t* post, int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int32_t* counts, int n_slots,
                 void* workspace, int64_t workspace_bytes, const rd_val_volume_t* volumes_host, int B, void* stream);
+
+/* TensorBoard image summaries (train.py --tb_images, ramdsir/tb_images.py), csrc/tb_grid.hip: replaces the make_grid(...) +
+ * writer.add_image(...) blocks of code/train.py:306-329 (Fundus) and :475-496 (Prostate) -- the slicing, sigmoid / tanh / argmax,
+ * decode_seg_map_sequence (code/utils/utils.py:285-336), torchvision.utils.make_grid and tensorboardX's float -> uint8 conversion --
+ * for ALL grids of one logging iteration in at most two launches.  torchvision and tensorboardX are not dependencies; their semantics
+ * are RESTATED here (parity unpinned) and modelled in numpy by ramdsir/tb_images.py grid_model:
+ *   selection   samples sample[0..n) (1 <= n <= 3) of the source, channels c0 .. c0 + nc (nc = 3, or nc = 1: replicated to three);
+ *               element (s, c, y, x) is src[s * stride_n + c * stride_c + y * stride_h + x * stride_w] (strides in ELEMENTS: the step's
+ *               NHWC buffers with a padded channel slot and contiguous NCHW tensors are both covered), bf16 widened to fp32;
+ *   transform   identity | sigmoid 1 / (1 + exp(-x)) | tanh | RD_TB_ARGMAX: argmax over the nc (= K <= RD_TB_PALETTE) channels from c0,
+ *               the lowest index winning a tie, then the palette | RD_TB_LABEL: the source is int64 [s][y][x] class labels, then the
+ *               palette.  Palette: the 21 "pascal" colours of decode_segmap, value float32(double(colour) / 255.0); a class outside it
+ *               stays black.  A Fundus target (fp32 0 / 1 planes) is RD_TB_F32 + identity without normalize;
+ *   normalize   make_grid(normalize=True): lo, hi = min, max over the whole selection after the transform;
+ *               v = (x - lo) / float32(max(double(hi) - double(lo), 1e-5)), an IEEE division (torchvision's norm_ip:
+ *               clamp_(low, high).sub_(low).div_(max(high - low, 1e-5)));
+ *   grid        make_grid(nrow=3, padding=2, pad_value=0): n == 1 -> the image itself, H x W; otherwise (H + 4) x (n (W + 2) + 2),
+ *               zero filled, tile k at rows [2, 2 + H), columns [k (W + 2) + 2, k (W + 2) + 2 + W);
+ *   pixel       add_image: uint8(trunc(v * 255.0f)), v in [0, 1] by construction;
+ *   dst         uint8 HWC [grid rows][grid columns][3] in a caller-owned device buffer.
+ * grids_host: n_grids (1 .. RD_TB_MAX_GRIDS) HOST records (read before the call returns: they travel as kernel arguments).  workspace:
+ * rd_tb_grids_workspace(n_grids) bytes, 8-byte aligned, contents irrelevant before and after (one (min, max) pair per workgroup of the
+ * first launch: no atomics, nothing to initialise; the launch is skipped when no grid normalises).  Launches on `stream`, never
+ * synchronises or copies (the caller reads dst with its own copy); -1 for an invalid record, before anything is launched.  The
+ * extents of src and dst are the caller's to guarantee. */
+enum { RD_TB_F32 = 0, RD_TB_BF16 = 1, RD_TB_I64 = 2 };
+enum { RD_TB_IDENTITY = 0, RD_TB_SIGMOID = 1, RD_TB_TANH = 2, RD_TB_ARGMAX = 3, RD_TB_LABEL = 4 };
+#define RD_TB_MAX_GRIDS 8
+#define RD_TB_PARTS 64
+#define RD_TB_PALETTE 21
+typedef struct {
+    const void* src;
+    uint8_t* dst;
+    int64_t stride_n, stride_c, stride_h, stride_w;   /* elements */
+    int32_t etype;              /* RD_TB_F32 / RD_TB_BF16; RD_TB_I64 with RD_TB_LABEL */
+    int32_t H, W;
+    int32_t n;                  /* selected samples, 1 .. 3 */
+    int32_t sample[3];
+    int32_t c0, nc;
+    int32_t transform;          /* RD_TB_* */
+    int32_t normalize;          /* not with RD_TB_ARGMAX / RD_TB_LABEL */
+    int32_t slot;               /* set by the library (whole 16-byte channel-slot loads apply); ignored on input */
+} rd_tb_grid_t;
+int64_t rd_tb_grids_workspace(int n_grids);
+int rd_tb_grids(const rd_tb_grid_t* grids_host, int n_grids, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
+ * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
+ * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */
+uint32_t rd_crc32c(const void* data, size_t n, uint32_t seed);
 
 /* Measurement only (bench.py `box`): what this box's GPU sustains on two fixed micro-kernels, so that a bench line can be compared across
  * boxes of a pool whose clocks differ by a few per cent.  No reference counterpart (the reference publishes no throughput: BASELINE.md).

@@ -117,6 +117,17 @@ class RdValVolume(C.Structure):
     _fields_ = [('off', i64), ('gt_off', i64), ('d', i32), ('h', i32), ('w', i32), ('slot', i32)]
 
 
+TB_F32, TB_BF16, TB_I64 = range(3)                                   # RD_TB_* element types
+TB_IDENTITY, TB_SIGMOID, TB_TANH, TB_ARGMAX, TB_LABEL = range(5)      # RD_TB_* transforms
+TB_MAX_GRIDS, TB_PALETTE = 8, 21
+
+
+class RdTbGrid(C.Structure):
+    _fields_ = [('src', vp), ('dst', vp), ('stride_n', i64), ('stride_c', i64), ('stride_h', i64), ('stride_w', i64), ('etype', i32),
+                ('H', i32), ('W', i32), ('n', i32), ('sample', i32 * 3), ('c0', i32), ('nc', i32), ('transform', i32),
+                ('normalize', i32), ('slot', i32)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -181,6 +192,9 @@ _SIGS = {
     'rd_run_list_bind_fork_events': (C.c_int, [C.c_int]),
     'rd_run_list_fork_counts': (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     'rd_run_list_fork_plan': (C.c_int, [C.POINTER(RdLaunch), C.c_int, C.POINTER(C.c_ubyte)]),
+    'rd_tb_grids_workspace': (i64, [C.c_int]),
+    'rd_tb_grids': (C.c_int, [C.POINTER(RdTbGrid), C.c_int, vp, i64, vp]),
+    'rd_crc32c': (C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),
     'rd_prostate_batch': (C.c_int, [C.POINTER(RdProstateBatch), C.POINTER(RdProstateSample), C.c_int, vp]),

@@ -193,6 +193,8 @@ class DataParallelStep:
         works = []
         if self.graphs is not None and (self.ts._slot != 0 or self.ts._x_ready or self.ts._next_loaded):
             raise RuntimeError('captured graphs replay the classical step on input slot 0: do not mix them with load_raw_next()')
+        if self.graphs is not None and self.ts._after_step is not None:
+            raise RuntimeError('captured graphs replay a fixed launch list: nothing can be armed behind their step')
         # segment -> bucket that is complete when it ends: A -> decoders (2), B1 -> deep encoder (1), B2 -> shallow (0)
         plan = ((0, 2), (1, 1), (2, 0))
         if self.graphs is not None:
@@ -226,4 +228,5 @@ class DataParallelStep:
         main.wait_stream(self.comm)
         self._run(3, main)
         if self.graphs is None:
+            self.ts.run_after_step()
             self.ts.advance()

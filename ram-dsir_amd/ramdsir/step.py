@@ -159,6 +159,7 @@ class TrainStep:
         self.rec_lane = bool(opt['rec_lane'])
         self.launch_threads = int(opt['launch_threads']) > 0 and self.fork      # (-1: DataParallelStep measures it; one process: one thread)
         self._slot1_keep = []
+        self._after_step = None
         self._ops = self._build_ops()
 
     def _build_ops(self):
@@ -408,6 +409,22 @@ class TrainStep:
             self._x_ready = False
         self._next_loaded = False
 
+    def arm_after_step(self, hook):
+        """hook(slot) is called ONCE, by the next step(), after the step's last launch has been enqueued and before the input slots
+        flip: `slot` is the input slot the step trained on.  Whatever the hook enqueues on the main stream runs behind the whole step
+        (every lane is joined in front of Adam) and in front of whatever the caller enqueues next -- the upload of the next mask into
+        the single target buffer in particular.  The buffers a reader wants at that point are all intact: every Act owns its
+        allocation (engine.Act), logits / rec_logits are written by the forward pass only, x[slot] is next written by the RAM of the
+        step after the next one.  The launch lists of the step are not touched.  A captured hipGraph replays a fixed list: refused."""
+        if self.graph is not None:
+            raise RuntimeError('a captured hipGraph replays a fixed launch list: nothing can be armed behind its step')
+        self._after_step = hook
+
+    def run_after_step(self):
+        hook, self._after_step = self._after_step, None
+        if hook is not None:
+            hook(self._slot)
+
     def capture(self):
         """Capture one step (zeroing + every launch) into a hipGraph on a side stream."""
         self._refuse_budgets_on_one_chain('capture()')
@@ -455,9 +472,12 @@ class TrainStep:
         if self.graph is not None:
             if self._slot != 0 or self._x_ready or self._next_loaded:
                 raise RuntimeError('a captured hipGraph replays the classical step on input slot 0: do not mix it with load_raw_next()')
+            if self._after_step is not None:
+                raise RuntimeError('a captured hipGraph replays a fixed launch list: nothing can be armed behind its step')
             self.graph.replay()
             return
         self.launch(self.head_names() + self.backward_names() + ('seg_c',), join_before_last=True)
+        self.run_after_step()
         self.advance()
 
     def loss_dict(self):

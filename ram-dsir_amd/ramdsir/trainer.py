@@ -28,6 +28,7 @@ class FusedTrainer:
                               options=dict(side_cus=0, rec_cus=0) if use_graph else None)
         self.ts.wpack.refresh()
         self._primed, self._graphs, self._announced = False, bool(use_graph), None
+        self._tb, self._tb_pending = None, None
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -68,6 +69,29 @@ class FusedTrainer:
             self.ts.load_target(next_batch[3])            # after the step has been enqueued: its loss still reads the current mask
         self._primed = pipelined
         self._announced = tuple(next_batch[:4]) if pipelined else None
+
+    def arm_tb_images(self):
+        """The next step() also composes the TensorBoard image grids of ITS batch (ramdsir/tb_images.py; code/train.py:306-329,
+        475-496) and starts their copy to pinned host memory; take_tb_images() then returns the pending result.  The compose is
+        enqueued behind the step's last launch and in front of the upload of the next mask (TrainStep.arm_after_step), reads the
+        input slot the step trained on, and only reads: training is bit-identical with and without it.  Not with use_graph=True."""
+        if self._graphs:
+            raise RuntimeError('arm_tb_images: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        from . import tb_images
+        ts = self.ts
+        if self._tb is None:
+            self._tb = tb_images.GridComposer(ts.dataset, ts.B, ts.H, ts.W, ts.K, self.bank.device)
+
+        def hook(slot):
+            self._tb_pending = self._tb.enqueue(tb_images.train_step_sources(ts, slot))
+        ts.arm_after_step(hook)
+
+    def take_tb_images(self):
+        """The tb_images.Pending of the last armed step (its images() waits for the copy), once."""
+        pending, self._tb_pending = self._tb_pending, None
+        if pending is None:
+            raise RuntimeError('take_tb_images: no armed step has run')
+        return pending
 
     def losses(self):
         """The five loss terms + per-domain rec losses (names of the tensorboard scalars, train.py:298-304).  Data parallel:
@@ -119,6 +143,18 @@ class ModuleTrainer:
         dev = next(encoder.parameters()).device
         self._ram = RamMixer(B, H, W, torch.float32, dev, dataset)
         self._ram_out = (torch.empty(B, H, W, 3, dtype=torch.float32, device=dev), torch.empty(B, H, W, 3, dtype=torch.float32, device=dev))
+        self._geom, self._tb, self._tb_armed, self._tb_pending = (B, H, W, dev), None, False, None
+
+    def arm_tb_images(self):
+        """As FusedTrainer.arm_tb_images: the next step() hands the tensors it holds -- img, img_freq, the soft prediction of the first
+        pass, the concatenated restored images, the target -- to rd_tb_grids (NCHW fp32, already transformed)."""
+        from . import tb_images
+        if self._tb is None:
+            B, H, W, dev = self._geom
+            self._tb = tb_images.GridComposer(self.dataset, B, H, W, self.num_classes, dev)
+        self._tb_armed = True
+
+    take_tb_images = FusedTrainer.take_tb_images
 
     def _mix(self, src_nhwc, trg_nhwc, lam):
         """(img, img_freq) NCHW fp32 in [-1, 1] (ram.source_to_target_freq_batch with the plan built once)."""
@@ -153,12 +189,13 @@ class ModuleTrainer:
             consistency = F.mse_loss(soft2, soft1)
         else:
             consistency = zero
-        loss, left, rec_l = 0, 0, []
+        loss, left, rec_l, rec_imgs = 0, 0, [], []
         for d, b in enumerate(self.bs):                                                         # train.py:265-276
             rec_soft = torch.tanh(self.rec(feats2[-1][left:left + b], domain_label=d * torch.ones(b, dtype=torch.long)))
             l = F.mse_loss(rec_soft, img[left:left + b])
             loss = loss + self.lambda_rec * l
             rec_l.append(l)
+            rec_imgs.append(rec_soft.detach())
             left += b
         loss = loss + seg1 + seg2 + dice1 + dice2 + 0.5 * consistency
         self.opt.zero_grad()
@@ -168,6 +205,10 @@ class ModuleTrainer:
         self.opt.param_groups[0]['lr'], self.opt.param_groups[1]['lr'], self.opt.param_groups[2]['lr'] = lr / 2, lr, lr
         self.iter_num += 1
         self._last = (seg1, dice1, seg2, dice2, consistency, loss, rec_l)
+        if self._tb_armed:
+            from . import tb_images
+            self._tb_armed = False
+            self._tb_pending = self._tb.enqueue(tb_images.module_sources(img, img_freq, soft1.detach(), torch.cat(rec_imgs, 0), target))
 
     def losses(self):
         seg1, dice1, seg2, dice2, cons, loss, rec_l = self._last

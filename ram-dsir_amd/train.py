@@ -10,8 +10,9 @@ Differences, all deliberate: (i) RAM runs on the GPU per batch (the DataLoader w
 image and lambda); (ii) the step is a static launch list enqueued ahead of the GPU, so the five loss scalars are read every
 --log_every iterations instead of forcing a device sync every iteration (train.py:298-304) -- and written, under the
 reference's tags, to a TensorBoard event file in <save_path>/log (utils/tfevents.py: tensorboardX is not a dependency);
-(iii) multi-GPU is one process per GPU with an RCCL gradient all-reduce instead of nn.DataParallel; (iv) tensorboard image
-grids and the source-tree snapshot (train.py:306-329,534-536) are not reproduced.
+(iii) multi-GPU is one process per GPU with an RCCL gradient all-reduce instead of nn.DataParallel; (iv) the tensorboard image
+grids (train.py:306-329, 475-496) are opt-in (--tb_images: composed on the GPU, ramdsir/tb_images.py) and the source-tree snapshot
+(train.py:534-536) is not reproduced.
 """
 import argparse
 import os
@@ -36,7 +37,7 @@ from dataset.fundus import Fundus_Multi, Fundus
 from dataset.prostate import Prostate_Multi
 from networks.unet import Encoder, Decoder, Rec_Decoder, count_params
 from utils.metrics import postprocessing, dice_coeff_2label, post_and_dice
-from utils.tfevents import SummaryWriter
+from utils.tfevents import SummaryWriter, QueuedWriter
 
 fundus_batch_list = [[3, 6, 7], [2, 7, 7], [2, 4, 10], [2, 4, 10]]              # train.py:35-38
 prostate_batch_list = [[2, 2, 2, 2, 2]] * 6                                       # train.py:40-45
@@ -93,6 +94,10 @@ def parse_args(argv=None):
     p.add_argument('--gpu_val_volumes', action='store_true',
                    help='prostate: keep the held-out site\'s volumes in device memory and build the 2.5-D batches, take the argmax, keep '
                         'the largest 3-D component and count for the Dice as HIP kernels; the reported numbers are those of the host path')
+    p.add_argument('--tb_images', type=int, nargs='?', const=100, default=0, metavar='N',
+                   help='also write the reference\'s TensorBoard image grids (input, RAM-mixed input, restored image, predictions, ground '
+                        'truth) of rank 0\'s batch every N iterations (100 as in the reference when N is omitted), composed by one HIP '
+                        'call from the step\'s buffers and encoded by a writer thread; off by default')
     return p.parse_args(argv)
 
 
@@ -287,6 +292,8 @@ def main(args):
         raise ValueError('only the --ram --rec flag combination exists in the reference; got ram=%s rec=%s' % (args.ram, args.rec))
     if args.gpu_val and args.dataset != 'fundus':
         raise ValueError('--gpu_val covers the in-training Fundus validation only; --dataset %s validates on the host' % args.dataset)
+    if args.tb_images < 0:
+        raise ValueError('--tb_images takes a positive interval, got %d' % args.tb_images)
     if args.gpu_val_volumes and args.dataset != 'prostate':
         raise ValueError('--gpu_val_volumes covers the in-training Prostate validation only; --dataset %s has --gpu_val' % args.dataset)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -386,7 +393,10 @@ def main(args):
                            consistency=cons, lambda_rec=args.lambda_rec, lr=args.lr, total_iters=total_iters,
                            dtype=torch.bfloat16 if (args.dtype or ('bf16' if args.norm == 'bn' else 'f32')) == 'bf16' else torch.float32)
 
-    writer = SummaryWriter(os.path.join(args.save_path, 'log')) if rank == 0 else None      # train.py:538
+    # --tb_images: one writer thread owns the event file (scalars go through its queue too, so the records keep the order of the
+    # calls); without the flag the direct writer, record for record what it always wrote
+    Writer = QueuedWriter if args.tb_images else SummaryWriter
+    writer = Writer(os.path.join(args.save_path, 'log')) if rank == 0 else None      # train.py:538
     previous_best, iter_num = 0.0, 0
     t_mark, it_mark, imgs_per_iter = None, 0, world * sum(bsl[:len(domain_idx_list)])
     for epoch in range(args.epochs):
@@ -416,6 +426,9 @@ def main(args):
             nxt = next(stream_it, None)
             last = nxt is None or bool(args.max_iters and iter_num + 1 >= args.max_iters)
             nxt = None if last else on_device(nxt)
+            log_images = rank == 0 and args.tb_images > 0 and iter_num % args.tb_images == 0      # train.py:306, 475
+            if log_images:
+                trainer.arm_tb_images()                 # this step also composes the grids of its batch and starts their copy
             trainer.step(*cur, next_batch=nxt)
             cur = nxt
             if iter_num % args.log_every == 0:
@@ -427,6 +440,8 @@ def main(args):
                 # the reference's scalars (train.py:298-304 / 467-473), at the iterations whose losses are read back
                 writer.add_scalars_at(iter_num, [('lr', lr_now)] + [('loss/' + k, v) for k, v in l.items() if k not in ('rec', 'loss')]
                                       + [('loss/loss_rec', sum(l['rec']) / 4)])
+            if log_images:                              # behind the scalars of the iteration, in the reference's tag order
+                writer.add_images_at(iter_num, trainer.take_tb_images())
             iter_num += 1
             if iter_num == 5:                           # end-to-end throughput (files -> DataLoader -> H2D -> step), start-up excluded
                 torch.cuda.synchronize()
@@ -475,6 +490,11 @@ def main(args):
         print('\nSave Final Model to {}'.format(args.save_path))
     if writer is not None:
         writer.close()
+        if args.tb_images and writer.seconds['calls']:
+            sec, n = writer.seconds, writer.seconds['calls']
+            print('tb_images: %d image records at %d iterations; writer thread per logging iteration: wait for the copy %.2f ms, PNG %.2f ms, '
+                  'crc32c + framing %.2f ms, file write %.2f ms' % (sec['records'], n, 1e3 * sec['wait'] / n, 1e3 * sec['png'] / n,
+                                                                    1e3 * sec['crc'] / n, 1e3 * sec['write'] / n))
     _close_val()
     _VAL_GPU.clear()
     _VAL_VOL.clear()

@@ -1,16 +1,21 @@
-"""Minimal TensorBoard event-file writer for scalars: what the reference's `tensorboardX.SummaryWriter(save_path + '/log')`
-produces for `writer.add_scalar(tag, value, iter_num)` (code/train.py:298-304, 467-473, 538).  tensorboardX / tensorboard are
-not installed here, so the three pieces are written out by hand:
+"""Minimal TensorBoard event-file writer for scalars and images: what the reference's `tensorboardX.SummaryWriter(save_path + '/log')`
+produces for `writer.add_scalar(tag, value, iter_num)` (code/train.py:298-304, 467-473, 538) and `writer.add_image(tag, grid, iter_num)`
+(train.py:306-329, 475-496).  tensorboardX / tensorboard are not installed here, so the three pieces are written out by hand:
 
   * TFRecord framing: uint64 length | masked crc32c(length) | payload | masked crc32c(payload), little endian;
   * crc32c (Castagnoli, reflected polynomial 0x82F63B78) with TensorFlow's mask ((crc >> 15 | crc << 17) + 0xa282ead8);
   * protobuf wire format of  Event { double wall_time = 1; int64 step = 2; string file_version = 3; Summary summary = 5; }
-    Summary { repeated Value value = 1; }   Value { string tag = 1; float simple_value = 2; }.
+    Summary { repeated Value value = 1; }   Value { string tag = 1; float simple_value = 2; Image image = 4; }
+    Image { int32 height = 1; int32 width = 2; int32 colorspace = 3; bytes encoded_image_string = 4; }.
 
 The first record of a file is Event{wall_time, file_version: "brain.Event:2"}; the file name follows TensorBoard's
 `events.out.tfevents.<unix time>.<hostname>` pattern so that `tensorboard --logdir <save_path>/log` picks it up.
-Image summaries (train.py:306-329) are out of scope.
+Image summaries take the finished uint8 HWC grid (train.py --tb_images composes it on the GPU: ramdsir/tb_images.py, which restates
+make_grid and tensorboardX's float -> uint8 conversion) and encode it as PNG with Pillow, as tensorboardX does.  The checksum of such a
+record (hundreds of kilobytes) goes through the HIP library's host routine rd_crc32c when the library is loadable; the pure-Python
+loop below is the fallback and the reference of the tests.
 """
+import io
 import os
 import socket
 import struct
@@ -24,15 +29,37 @@ for _i in range(256):
     _TABLE.append(_c)
 
 
-def crc32c(data):
-    c = 0xFFFFFFFF
+def crc32c(data, seed=0):
+    """Pure Python; seed: the crc of the bytes in front of `data` (0 for none)."""
+    c = seed ^ 0xFFFFFFFF
     for b in data:
         c = _TABLE[(c ^ b) & 0xFF] ^ (c >> 8)
     return c ^ 0xFFFFFFFF
 
 
+_native = None
+
+
+def _native_crc32c():
+    """rd_crc32c of the HIP library (host code), or False when the library cannot be loaded (not built, no ROCm runtime)."""
+    global _native
+    if _native is None:
+        try:
+            from ramdsir import _lib
+            _native = _lib.lib().rd_crc32c
+        except Exception:
+            _native = False
+    return _native
+
+
+def crc32c_fast(data, seed=0):
+    """crc32c(data) through rd_crc32c when available (seed: the crc of the bytes in front), else the Python loop."""
+    fn = _native_crc32c() if len(data) >= 64 else None          # (a ctypes call costs more than 64 table steps)
+    return fn(bytes(data), len(data), seed) if fn else crc32c(data, seed)
+
+
 def masked_crc(data):
-    c = crc32c(data)
+    c = crc32c_fast(data)
     return (((c >> 15) | (c << 17)) + 0xA282EAD8) & 0xFFFFFFFF
 
 
@@ -57,8 +84,22 @@ def _bytes_field(field, payload):
     return _key(field, 2) + _varint(len(payload)) + payload
 
 
-def encode_event(wall_time, step=None, file_version=None, scalars=None):
-    """scalars: list of (tag, float)."""
+def encode_png(img_hwc_uint8):
+    """PNG bytes of a uint8 (H, W, 3) / (H, W, 1) / (H, W) array (Pillow, as tensorboardX's make_image)."""
+    import numpy as np
+    from PIL import Image
+    a = np.ascontiguousarray(img_hwc_uint8)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
+        raise ValueError('add_image takes a uint8 HWC array with 1 or 3 channels, got %s %s' % (a.dtype, a.shape))
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    buf = io.BytesIO()
+    Image.fromarray(a).save(buf, format='PNG')
+    return a.shape[0], a.shape[1], (3 if a.ndim == 3 else 1), buf.getvalue()
+
+
+def encode_event(wall_time, step=None, file_version=None, scalars=None, images=None):
+    """scalars: list of (tag, float); images: list of (tag, height, width, colorspace, png bytes)."""
     ev = _key(1, 1) + struct.pack('<d', wall_time)
     if step is not None:
         ev += _key(2, 0) + _varint(int(step))
@@ -70,6 +111,12 @@ def encode_event(wall_time, step=None, file_version=None, scalars=None):
             val = _bytes_field(1, tag.encode()) + _key(2, 5) + struct.pack('<f', float(v))
             summ += _bytes_field(1, val)
         ev += _bytes_field(5, summ)
+    if images:
+        summ = b''
+        for tag, h, w, cs, png in images:
+            im = _key(1, 0) + _varint(h) + _key(2, 0) + _varint(w) + _key(3, 0) + _varint(cs) + _bytes_field(4, bytes(png))
+            summ += _bytes_field(1, _bytes_field(1, tag.encode()) + _bytes_field(4, im))
+        ev += _bytes_field(5, summ)
     return ev
 
 
@@ -79,7 +126,8 @@ def frame(payload):
 
 
 class SummaryWriter(object):
-    """`add_scalar(tag, scalar_value, global_step)` / `flush()` / `close()` of tensorboardX.SummaryWriter."""
+    """`add_scalar(tag, scalar_value, global_step)` / `add_image(tag, img, global_step)` / `flush()` / `close()` of
+    tensorboardX.SummaryWriter (add_image with dataformats='HWC' and a finished uint8 image)."""
 
     def __init__(self, logdir, flush_secs=30):
         os.makedirs(logdir, exist_ok=True)
@@ -100,6 +148,13 @@ class SummaryWriter(object):
         if t - self._last > self._flush_secs:
             self.flush()
 
+    def add_image(self, tag, img_hwc_uint8, global_step=None, walltime=None):
+        """One Summary.Value{tag, image} record: the uint8 HWC array as PNG."""
+        t = time.time() if walltime is None else walltime
+        self._f.write(frame(encode_event(t, step=global_step, images=[(tag,) + encode_png(img_hwc_uint8)])))
+        if t - self._last > self._flush_secs:
+            self.flush()
+
     def flush(self):
         self._f.flush()
         self._last = time.time()
@@ -108,6 +163,76 @@ class SummaryWriter(object):
         if not self._f.closed:
             self._f.flush()
             self._f.close()
+
+
+class QueuedWriter(SummaryWriter):
+    """A SummaryWriter whose records are encoded and written by ONE thread that owns the file (train.py --tb_images): the training
+    thread only enqueues.  add_scalars_at takes its wall time at the call, as the direct writer does; add_images_at(step, fetch)
+    takes a callable that returns [(tag, uint8 HWC array)] when the data has arrived (ramdsir.tb_images.Pending: it waits for the
+    event behind the device-to-host copy) -- PNG encoding (zlib, Pillow: both release the GIL), checksums and the write happen in the
+    thread.  Records appear in the order of the calls.  close() drains the queue; an error in the thread is raised there."""
+
+    def __init__(self, logdir, flush_secs=30):
+        import queue
+        import threading
+        SummaryWriter.__init__(self, logdir, flush_secs)
+        self._q, self._err = queue.Queue(), None
+        self.seconds = dict(wait=0.0, png=0.0, crc=0.0, write=0.0, records=0, calls=0)      # host time of the image records (profiles/tb_images.md)
+        self._t = threading.Thread(target=self._drain, name='tfevents-writer', daemon=True)
+        self._t.start()
+
+    def add_scalars_at(self, global_step, pairs, walltime=None):
+        self._q.put(('scalars', global_step, list(pairs), time.time() if walltime is None else walltime))
+
+    def add_images_at(self, global_step, fetch, walltime=None):
+        self._q.put(('images', global_step, fetch, time.time() if walltime is None else walltime))
+
+    def add_image(self, tag, img_hwc_uint8, global_step=None, walltime=None):
+        self.add_images_at(global_step, lambda: [(tag, img_hwc_uint8)], walltime)
+
+    def _drain(self):
+        while True:
+            item = self._q.get()
+            if item is None:
+                return
+            if self._err is not None:
+                continue                    # keep consuming so that close() never blocks
+            try:
+                kind, step, payload, t = item
+                if kind == 'scalars':
+                    SummaryWriter.add_scalars_at(self, step, payload, t)
+                    continue
+                sec = self.seconds
+                t0 = time.perf_counter()
+                images = payload()
+                t1 = time.perf_counter()
+                sec['wait'] += t1 - t0
+                sec['calls'] += 1
+                for tag, img in images:
+                    t1 = time.perf_counter()
+                    ev = encode_event(t, step=step, images=[(tag,) + encode_png(img)])
+                    t2 = time.perf_counter()                 # (the protobuf wrapping counts as PNG time: a few byte joins)
+                    rec = frame(ev)
+                    t3 = time.perf_counter()
+                    self._f.write(rec)
+                    t4 = time.perf_counter()
+                    sec['png'] += t2 - t1
+                    sec['crc'] += t3 - t2
+                    sec['write'] += t4 - t3
+                    sec['records'] += 1
+                if t - self._last > self._flush_secs:
+                    self.flush()
+            except Exception as e:          # noqa: BLE001 -- reported by close()
+                self._err = e
+
+    def close(self):
+        if self._t.is_alive():
+            self._q.put(None)
+            self._t.join()
+        SummaryWriter.close(self)
+        if self._err is not None:
+            err, self._err = self._err, None
+            raise err
 
 
 # ---------------------------------------------------------------------------------------------- reader (tests, tooling)
@@ -142,7 +267,8 @@ def _fields(buf):
 
 
 def read_events(path):
-    """-> list of dicts {wall_time, step, file_version, scalars: [(tag, value)]}; every CRC is verified."""
+    """-> list of dicts {wall_time, step, file_version, scalars: [(tag, value)], images: [(tag, height, width, colorspace, png bytes)]};
+    every CRC is verified."""
     out = []
     with open(path, 'rb') as f:
         data = f.read()
@@ -156,7 +282,7 @@ def read_events(path):
         if c1 != masked_crc(head) or c2 != masked_crc(payload) or len(payload) != n:
             raise ValueError('corrupt record at byte %d' % pos)
         pos += 16 + n
-        ev = dict(wall_time=None, step=0, file_version=None, scalars=[])
+        ev = dict(wall_time=None, step=0, file_version=None, scalars=[], images=[])
         for field, wire, v in _fields(payload):
             if field == 1:
                 ev['wall_time'] = struct.unpack('<d', v)[0]
@@ -168,12 +294,17 @@ def read_events(path):
                 for f1, _, val in _fields(v):
                     if f1 != 1:
                         continue
-                    tag, sv = None, None
+                    tag, sv, im = None, None, None
                     for f2, _, x in _fields(val):
                         if f2 == 1:
                             tag = x.decode()
                         elif f2 == 2:
                             sv = struct.unpack('<f', x)[0]
-                    ev['scalars'].append((tag, sv))
+                        elif f2 == 4:
+                            im = {f3: y for f3, _, y in _fields(x)}
+                    if im is not None:
+                        ev['images'].append((tag, im.get(1, 0), im.get(2, 0), im.get(3, 0), bytes(im.get(4, b''))))
+                    else:
+                        ev['scalars'].append((tag, sv))
         out.append(ev)
     return out
