@@ -35,7 +35,8 @@ def normalization(planes, norm='gn', num_domains=None):
 
 
 def _plan_for(mod, key, N, training, build_graph, device):
-    """Acquire (or build) the launch plan of a module called on its own."""
+    """Acquire (or build) the launch plan of a module called on its own.  build_graph(pl) adds the module's graph to the new plan
+    and leaves its inputs / outputs on it (pl.x_in / pl.ins, pl.out / pl.feats)."""
     def build():
         pl = E.Plan(mod._bank, M.storage_dtype(), N, M.group_starts(getattr(mod, '_norm', 'bn'), N), slope=mod._slope, training=training)
         build_graph(pl)
@@ -194,19 +195,13 @@ class Encoder(M.FusedModule):
             parts = [self.forward(x[a:b]) for a, b in chunks]
             return [torch.cat([q[k] for q in parts], 0) for k in range(len(parts[0]))]
         self._ensure_bound(x.device)
-        training = self._bn_training()
 
-        def build():
-            pl = E.Plan(self._bank, M.storage_dtype(), N, M.group_starts(self._norm, N), slope=self._slope, training=training)
+        def graph(pl):
             pl.x_in = E.Act(pl, N, H, W, Cc, name='input')
             pl.feats = E.build_encoder(pl, pl.x_in, n=self._n, mname=self._mname, norm=self._norm)
             for a in pl.feats:
                 a.g_written = True                      # their gradient arrives from torch first (rd_grad_in)
-            pl.build(self._wpack)
-            pl.ws = E.workspace(pl.ws_bytes // 4, x.device)
-            pl.bind_workspace(pl.ws)
-            return pl
-        pl = self._acquire_plan((N, H, W, training, M.storage_dtype()), build)
+        pl = _plan_for(self, (N, H, W), N, self._bn_training(), graph, x.device)
         return list(M.run_fused(self, pl, [pl.x_in], pl.feats, [x]))
 
 
@@ -232,23 +227,13 @@ class Decoder(M.FusedModule):
         if chunks is not None:
             return torch.cat([self.forward([f[a:b] for f in feats]) for a, b in chunks], 0)
         self._ensure_bound(feats[0].device)
-        training = self._bn_training()
 
-        def build():
-            pl = E.Plan(self._bank, M.storage_dtype(), N, M.group_starts(self._norm, N), slope=self._slope, training=training)
-            pl.ins = []
-            for f in feats:
-                a = E.Act(pl, N, f.shape[2], f.shape[3], f.shape[1], name='feat')
-                a.needs_grad = True
-                pl.ins.append(a)
-            pl.logits = E.build_decoder(pl, pl.ins, n=self._n, num_classes=self._k, mname=self._mname, norm=self._norm)
-            pl.logits.g_written = True
-            pl.build(self._wpack)
-            pl.ws = E.workspace(pl.ws_bytes // 4, feats[0].device)
-            pl.bind_workspace(pl.ws)
-            return pl
-        pl = self._acquire_plan((shapes, training, M.storage_dtype()), build)
-        return M.run_fused(self, pl, pl.ins, [pl.logits], list(feats))[0]
+        def graph(pl):
+            pl.ins = [_raw_input(pl, f, 'feat') for f in feats]
+            pl.out = E.build_decoder(pl, pl.ins, n=self._n, num_classes=self._k, mname=self._mname, norm=self._norm)
+            pl.out.g_written = True
+        pl = _plan_for(self, (shapes,), N, self._bn_training(), graph, feats[0].device)
+        return M.run_fused(self, pl, pl.ins, [pl.out], list(feats))[0]
 
 
 class Rec_Decoder(M.FusedModule):
@@ -273,18 +258,11 @@ class Rec_Decoder(M.FusedModule):
         d = int(domain_label[0]) if domain_label is not None else None         # dsbn.py:26
         N, Cc, H, W = x.shape
         self._ensure_bound(x.device)
-        training = self._bn_training()
 
-        def build():
-            pl = E.Plan(self._bank, M.storage_dtype(), N, [0, N], slope=self._slope, training=training)
-            pl.x_in = E.Act(pl, N, H, W, Cc, name='bottleneck')
-            pl.x_in.needs_grad = True
+        def graph(pl):
+            pl.x_in = _raw_input(pl, x, 'bottleneck')
             pl.out = E.build_rec_decoder(pl, pl.x_in, 0, -1, [d] if self._dsbn else None, n=self._n, num_classes=self._k,
                                          mname=self._mname)
             pl.out.g_written = True
-            pl.build(self._wpack)
-            pl.ws = E.workspace(pl.ws_bytes // 4, x.device)
-            pl.bind_workspace(pl.ws)
-            return pl
-        pl = self._acquire_plan((N, Cc, H, W, d, training, M.storage_dtype()), build)
+        pl = _plan_for(self, (N, Cc, H, W, d), N, self._bn_training(), graph, x.device)
         return M.run_fused(self, pl, [pl.x_in], [pl.out], [x])[0]

@@ -15,6 +15,7 @@ Design (MI355X-first):
     max-pool scatter, skip accumulation) and the two BN-backward sums; BN backward itself is the
     per-channel P*g+Q*z+R folded into the reads of the next dgrad / wgrad.
 """
+import collections
 import ctypes as C
 import os
 
@@ -243,6 +244,7 @@ class Act:
         self.buf = plan.alloc_act((N, H, W, self.Cs))
         self.g = None                 # gradient w.r.t. the BN output (hi-res when up)
         self.g_written = False
+        self.needs_grad = False       # a tensor without a producer in the plan (a module's input) whose gradient is wanted all the same
         G = plan.G
         if norm is not None:
             self.stats = plan.alloc_stat(G * L.STAT_SLOTS * Cc * 2)
@@ -251,7 +253,13 @@ class Act:
             self.mean, self.invstd = plan.alloc_f32(G * Cc), plan.alloc_f32(G * Cc)
             self.P, self.Q, self.R = plan.alloc_f32(G * Cc), plan.alloc_f32(G * Cc), plan.alloc_f32(G * Cc)
         else:
-            self.stats = self.bstats = self.scale = self.shift = None
+            self.stats = self.bstats = self.scale = self.shift = self.mean = self.invstd = self.P = self.Q = self.R = None
+        # set by Plan.build.  A FOLDED BatchNorm finalize (rd_src_t.fin): the address of the host descriptor, which the entry point copies
+        # into the kernel arguments at launch time (Plan.keep holds the descriptor); None where the site keeps its explicit launch
+        self.fin_fwd, self.fin_fwd_op, self.fin_fwd_taken = None, None, False     # forward: descriptor, the explicit launch, claimed yet
+        self.fin_bwd = None
+        self.dt_buf = None            # up: the gradient w.r.t. the low-res tensor (rd_up_bwd)
+        self.dz_store = None          # dz as the gradient launch's loader stores it for the weight gradient (rd_src_t.out)
 
     def grad_buf(self):
         if self.g is None:
@@ -265,58 +273,95 @@ class ConvNode:
         self.mname, self.name, self.inputs, self.out = mname, name, inputs, out
         self.taps, self.Cin, self.Cout = taps, Cin, Cout
         self.has_bias_grad = has_bias_grad          # out1 convs: live bias (no BN behind it)
+        # set by Plan.build
+        self.a_store = [None] * len(inputs)         # per input: the operand as the forward launch's loader stores it (rd_src_t.out)
+        self.wg = None                              # weight-gradient descriptor (training plans)
+        self.fused = False                          # gradient + weight gradient in one launch
+        self.fused_ws = self.bias_ws = None         # per-layer workspaces of the fused launch / the bias column sum
+        self.side_meta = []                         # meta dicts of this layer's side-lane launches (bind_workspace sets side_idx)
 
 
 class PoolNode:
     """nn.MaxPool2d(2) in front of a ConvD (unet.py:56), materialised: `out` = maxpool2(act(bn(src))) stored once."""
     def __init__(self, mname, name, src, out):
         self.mname, self.name, self.src, self.out = mname, name, src, out
+        self.wg = None                              # (no weights: Plan.bind_workspace walks all nodes)
+
+
+# tuning.py fold_finalize, decoded: which BatchNorm finalize launches are folded into the prologue of a launch that reads the coefficients
+# (rd_src_t.fin, csrc/bn_fin.h).  Plan reads these facts, never the integer.
+#   fwd        the forward ones (into the first forward launch that reads scale / shift: Plan._take_fwd_fin)
+#   bwd_fused  the backward ones of layers whose gradient and weight gradient are ONE launch (rd_conv_bwd_fused)
+#   bwd_pair   the backward ones of layers with stand-alone launches (the gradient launch as owner, the weight gradient beside it)
+#   bwd_up     the backward ones of upsampled 1x1 layers, into rd_up_bwd
+#   none       timing experiment: decides like 1, but the finalizes are neither folded nor launched (wrong results)
+Fold = collections.namedtuple('Fold', 'fwd bwd_fused bwd_pair bwd_up none')
+FOLD_FINALIZE = {
+    0: Fold(False, False, False, False, False),      # explicit rd_bn_finalize_* launches
+    1: Fold(True, True, True, True, False),
+    2: Fold(True, True, True, True, True),
+    3: Fold(True, False, False, False, False),
+    4: Fold(False, True, True, True, False),
+    5: Fold(True, True, False, True, False),
+    6: Fold(True, True, False, False, False),
+}
 
 
 class Plan:
     """Buffers + launch lists for one batch geometry (N images in G groups at H x W)."""
 
-    def __init__(self, bank, dtype, N, gstart, slope=0.0, training=True):
+    def __init__(self, bank, dtype, N, gstart, slope=0.0, training=True, options=None, fused_step=False, pad_narrow=False,
+                 side_cus=0, conv_cus=0, dgrad_cus=0):
+        """options: a full option set (tuning.options(...)); None: the process-wide one.  The facts of THIS plan are arguments:
+        fused_step   a plan of the fused training step.  False (a module called on its own, an eval plan) never folds a BatchNorm
+                     finalize and stores neither y = up2(t) nor act(bn(z)) / dz, whatever the options say
+        pad_narrow   pad the dlogits of the output convs to one 16-byte slot
+        side_cus     >0: compute-unit budget of the weight-gradient launches (they run on a side stream)
+        conv_cus     >0: ... of this plan's persistent conv launches (a side-lane plan)
+        dgrad_cus    >0: ... of its >= 64-channel gradient launches only (tuning.py dgrad_cus)"""
+        opt = T.options() if options is None else options
         self.bank, self.dtype = bank, dtype
         self.dt = L.RD_BF16 if dtype == torch.bfloat16 else L.RD_F32
         self.device = bank.device
         self.N, self.gstart, self.G = N, list(gstart), len(gstart) - 1
         self.slope, self.training = slope, training
-        self.pad_narrow = False       # TrainStep: pad the dlogits of the output convs to one 16-byte slot
+        self.pad_narrow = bool(pad_narrow)
+        self.side_cus, self.conv_cus, self.dgrad_cus = int(side_cus), int(conv_cus), int(dgrad_cus)
         # True: rd_up_stats also stores y = up2(t), and the 3x3 conv behind it (forward, dgrad epilogue, wgrad)
         # reads y as a plain BN+ReLU source instead of interpolating t four-taps-per-pixel in every loader:
         # +1 write / +3 reads of y against ~40% less time in those three kernels (DESIGN.md, 'upsample')
-        self.materialize_up = False
+        self.materialize_up = bool(fused_step and opt['up_mat'])
         # True: the 2x2 max-pool in front of ConvD levels 2-5 is stored once (rd_pool_fwd, 1/4 of the pixels) and its
         # gradient scattered by rd_pool_bwd, so the conv behind it runs the plain-source kernels in forward, dgrad and
         # wgrad (level 2 at 400x400, 16 images: 576 -> ~230 us for the three launches; profiles/README.md round 2).
         # False: RD_SRC_POOL / RD_DST_POOL fused into the conv's tile loader / gradient epilogue.
-        self.materialize_pool = T.options()['pool_mat']
-        self.side_cus = 0               # >0: compute-unit budget of the weight-gradient launches (they run on a side stream)
-        self.conv_cus = 0               # >0: compute-unit budget of this plan's persistent conv launches (a side-lane plan)
-        self.dgrad_cus = 0              # >0: ... of its >= 64-channel gradient launches only (tuning.py dgrad_cus)
-        self.materialize_min_c = None   # channels from which BN+ReLU outputs are stored once (rd_bn_apply)
-        self.materialize_dz_min_c = None  # ... and from which the BN-backward gradients dz are
-        self.materialize_dz_wide = bool(T.options()['mat_dz_wide'])
-        self.fused_bwd = bool(T.options()['fused_bwd'])   # small-channel 3x3 convs: dgrad + weight gradient in one launch
+        self.materialize_pool = bool(opt['pool_mat'])
+        # channels from which BN+ReLU outputs are stored once (rd_bn_apply) ... and from which the BN-backward gradients dz are
+        self.materialize_min_c = opt['mat_min_c'] if (fused_step and opt['mat_min_c'] > 0) else None
+        self.materialize_dz_min_c = opt['mat_dz_min_c'] if (fused_step and opt['mat_dz_min_c'] > 0) else None
+        self.materialize_dz_wide = bool(opt['mat_dz_wide'])
+        self.fused_bwd = bool(opt['fused_bwd'])   # small-channel 3x3 convs: dgrad + weight gradient in one launch
         # True: a conv launch that runs on the warp-specialised 64-wide kernel also STORES what its loader waves stage (rd_src_t.out:
         # act(bn(z)) in the forward launch, dz in the gradient launch), and the layer's weight gradient reads those stored operands
         # (RD_SRC_RAW: its loader copies instead of repeating the transforms, and the loader is that kernel's pole)
-        self.store_operands = int(T.options()['store_wgrad_operands'])     # bit 0: the forward operand, bit 1: dz
-        self.store_min_c = int(T.options()['store_wgrad_min_c'])           # ... of tensors with at least this many channels only
-        self.split_wide_dgrad = bool(T.options()['split_wide_dgrad'])   # _dgrad_halves below
-        # True (the fused training step): no BatchNorm finalize launches between the convs -- the launch that first reads a layer's
-        # coefficients derives them from the statistic slots in its prologue (rd_src_t.fin, csrc/bn_fin.h), and every launch spreads
-        # its sums over RD_STAT_SLOTS_FOLD copies only.  False: explicit rd_bn_finalize_* launches (modules, eval plans, gn / in)
-        self.fold_finalize = False
-        self.fold_wgrad_behind = bool(T.options()['fold_wgrad_behind'])
-        self.fold_fwd_kinds = int(T.options()['fold_fwd_kinds'])
+        self.store_operands = int(opt['store_wgrad_operands'])     # bit 0: the forward operand, bit 1: dz
+        self.store_min_c = int(opt['store_wgrad_min_c'])           # ... of tensors with at least this many channels only
+        self.split_wide_dgrad = bool(opt['split_wide_dgrad'])   # _dgrad_halves below
+        # != 0 (the fused training step): no BatchNorm finalize launches between the convs -- the launch that first reads a layer's
+        # coefficients derives them from the statistic slots in its prologue, and every launch spreads its sums over
+        # RD_STAT_SLOTS_FOLD copies only.  0: explicit rd_bn_finalize_* launches (modules, eval plans, gn / in)
+        self.fold_finalize = int(opt['fold_finalize']) if fused_step else 0
+        self.fold = FOLD_FINALIZE[self.fold_finalize]
+        self.fold_wgrad_behind = bool(opt['fold_wgrad_behind'])
+        self.fold_fwd_kinds = int(opt['fold_fwd_kinds'])
         self._unit = {}
         self.nodes = []
         self.keep = []
         self._stat_chunks = []
         self.fwd, self.bwd = [], []
+        self.fwd_split, self.bwd_split, self.bwd_node_start = {}, {}, {}
         self.ws_bytes = 0
+        self.wpack, self.nsl = None, 0          # build(): the packed weights, stat_slots()
         if self.G > L.MAXG:
             raise ValueError('%d statistics groups (gn / in: one per image), the kernels take at most %d' % (self.G, L.MAXG))
         self.gs_arr = L.gstart_array(self.gstart)
@@ -401,25 +446,18 @@ class Plan:
             return n
         return L.STAT_SLOTS_FOLD if self.fold_finalize else 0
 
-    def _folds(self, o, direction='fwd'):
-        """The finalize launches of Act `o` are folded into their consumers: BatchNorm in training mode, coefficients read through
-        scale / shift resp. P / Q / R by launches that take a `fin` (not the materialising rd_bn_apply passes).  fold_finalize: 1 both
-        directions, 3 the forward finalizes only, 4 the backward ones only (2: timing experiment, none at all)."""
-        if o.plan.fold_finalize == (4 if direction == 'fwd' else 3):      # (5 / 6: Plan.build un-folds part of the backward ones)
-            return False
-        return bool(o.plan.fold_finalize and o.plan.training and o.norm is not None and o.norm.kind == 'bn' and o.a_buf is None
-                    and o.plan.materialize_dz_min_c is None and not o.plan.split_wide_dgrad and o.plan.G <= L.FIN_MAX_G)
-
-    def _fin_ptr(self, desc):
-        """rd_src_t.fin of a consumer: the address of the (host) finalize descriptor, which the entry point copies into the kernel
-        arguments at launch time.  The descriptor is kept alive by Plan.keep."""
-        return C.addressof(desc)
+    def _can_fold(self, o):
+        """The finalize launches of this plan's Act `o` CAN be folded into their consumers (self.fold says which are): BatchNorm in
+        training mode, coefficients read through scale / shift resp. P / Q / R by launches that take a `fin` (not the materialising
+        rd_bn_apply passes)."""
+        return bool(self.training and o.norm is not None and o.norm.kind == 'bn' and o.a_buf is None
+                    and self.materialize_dz_min_c is None and not self.split_wide_dgrad and self.G <= L.FIN_MAX_G)
 
     def _take_fwd_fin(self, a, kind=1):
         """(fin, flags) for a FORWARD launch of this plan that reads Act a's scale / shift.  The first consumer inside the owning plan
         is the owner and later ones (same stream, behind it) need nothing; a consumer in ANOTHER plan runs on another lane, possibly
         beside the owner, so it derives the coefficients itself (restoration decoder on the encoder bottleneck)."""
-        if getattr(a, 'fin_fwd', None) is None or self.fold_finalize == 2:      # 2: timing experiment -- no finalize at all (wrong results)
+        if a.fin_fwd is None:
             return None, 0
         if not (self.fold_fwd_kinds & kind) and a.plan is self and not a.fin_fwd_taken:
             # this kind of consumer (1 small-channel conv, 2 wide conv, 4 max-pool: tuning.py fold_fwd_kinds) keeps the explicit launch, in front of it
@@ -481,288 +519,331 @@ class Plan:
         else:
             s.ptr, s.ptr2, s.mode = o.grad_buf().data_ptr(), o.buf.data_ptr(), L.SRC_BNBWD
             s.scale, s.shift, s.q = o.P.data_ptr(), o.R.data_ptr(), o.Q.data_ptr()
-            if owner is not None and getattr(o, 'fin_bwd', None) is not None and self.fold_finalize != 2:
+            if owner is not None and o.fin_bwd is not None:
                 s.fin, s.fin_flags = o.fin_bwd, (L.FIN_OWNER if owner else 0)
         return s
 
+    # ---- launch lists: one emitter per kind of node, in the order the launches run
     def build(self, wpack):
         """wpack: WeightPack giving packed-weight pointers per (module, conv name)."""
-        lib = L.lib()
+        self.wpack, self.nsl = wpack, self.stat_slots()
         self.finalize_stats()
-        dt = self.dt
-        nsl = self.stat_slots()
-        ws_need = 0
-        self.fwd_split = {}
         for node in self.nodes:
-            o = node.out
-            H, W, N = o.H, o.W, o.N
-            if node.mname not in self.fwd_split:
-                self.fwd_split[node.mname] = len(self.fwd)
+            self.fwd_split.setdefault(node.mname, len(self.fwd))
             if isinstance(node, PoolNode):
-                a = node.src
-                has_bn = a.norm is not None
-                fin, fin_flags = self._take_fwd_fin(a, 4) if has_bn else (None, 0)
-                self.fwd.append((lib.rd_pool_fwd, (a.buf.data_ptr(), a.scale.data_ptr() if has_bn else None, a.shift.data_ptr() if has_bn else None,
-                                                   self.slope if (has_bn and a.act) else 1.0, o.buf.data_ptr(), N, H, W, o.C, self.G, self.gs_arr, dt,
-                                                   fin, fin_flags),
-                                 dict(kernel='pool', what='fwd', layer='%s.%s' % (node.mname, node.name))))
-                continue
-            # ---------------- forward conv
-            p = L.RdConv()
-            p.cu_limit = int(self.conv_cus)
-            p.stat_slots = nsl
-            small = node.Cin <= 32 and node.Cout <= 32
-            for i, (a, mode, n_off, g_fixed) in enumerate(node.inputs):
-                p.src[i] = self._src(a, mode, n_off, g_fixed, fold=1 if small else 2)
-            p.nsrc, p.taps = len(node.inputs), node.taps
-            p.w = wpack.ptr(node.mname, node.name, False)
-            p.bias = self.bank.p(node.mname, node.name + '.bias').data_ptr()
-            p.CinPad, p.CoutPad = wpack.pads(node.Cout, node.Cin)
-            p.N, p.H, p.W, p.Cin, p.Cout = N, H, W, node.Cin, node.Cout
-            p.G, p.gstart = self.G, self.gs_arr
-            p.emode, p.out = 0, o.buf.data_ptr()
-            p.stats = o.plan.stat_ptr(o.stats) if (o.norm is not None and not o.up) else None
-            node.a_store = [None] * len(node.inputs)
-            if ((self.store_operands & 1) and self.training and self.dtype == torch.bfloat16 and node.taps == 9 and node.Cin >= self.store_min_c
-                    and lib.rd_conv_honours_src_out(C.byref(p), dt)):
-                for i, (a, mode, n_off, g_fixed) in enumerate(node.inputs):
-                    if p.src[i].mode in (L.SRC_AFF, L.SRC_AFFACT):
-                        src_t = a.y_buf if (mode == L.SRC_UP and a.y_buf is not None) else a.buf
-                        node.a_store[i] = self.alloc_act(tuple(src_t.shape))
-                        p.src[i].out = node.a_store[i].data_ptr()
-            self.keep.append(p)
-            self.fwd.append((lib.rd_conv, (C.byref(p), dt), self._conv_meta(node, N, H, W, node.Cin, node.Cout, 'fwd')))
-            if o.norm is not None:
-                if o.up:
-                    self.fwd.append((lib.rd_up_stats, (o.buf.data_ptr(), o.plan.stat_ptr(o.stats), o.y_buf.data_ptr() if o.y_buf is not None else None,
-                                                        N, H, W, o.C, self.G, self.gs_arr, dt, nsl)))
-                b = L.RdBnFwd()
-                b.stats = o.plan.stat_ptr(o.stats)
-                # the conv epilogues sum the result WITHOUT its bias; rd_up_stats sums y = up2(t) itself
-                b.conv_bias = None if o.up else self.bank.p(node.mname, node.name + '.bias').data_ptr()
-                b.scale, b.shift, b.mean, b.invstd = o.scale.data_ptr(), o.shift.data_ptr(), o.mean.data_ptr(), o.invstd.data_ptr()
-                hw = (4 if o.up else 1) * H * W
-                kind = o.norm.kind
-                if kind != 'bn' and any(self.gstart[g + 1] - self.gstart[g] != 1 for g in range(self.G)):
-                    raise ValueError('norm=%r needs a launch plan with one statistics group per image (gstart = 0..N)' % kind)
-                for g in range(self.G):
-                    b.gamma[g] = o.norm.gamma_ptr(self, g, o.C)
-                    b.beta[g] = o.norm.beta_ptr(self, g, o.C)
-                    b.running_mean[g] = o.norm.buf_ptr(g, 'running_mean')
-                    b.running_var[g] = o.norm.buf_ptr(g, 'running_var')
-                    b.num_batches_tracked[g] = o.norm.buf_ptr(g, 'num_batches_tracked')
-                    b.count[g] = float((self.gstart[g + 1] - self.gstart[g]) * hw)
-                # gn / in always normalise with the statistics of the input itself (nn.GroupNorm / nn.InstanceNorm2d in eval mode too)
-                b.C, b.G, b.eps, b.momentum, b.training = o.C, self.G, EPS, MOMENTUM, 1 if (self.training or kind != 'bn') else 0
-                b.nslots = nsl
-                self.keep.append(b)
-                o.bn_desc = b
-                if self._folds(o):
-                    o.fin_fwd, o.fin_fwd_taken = self._fin_ptr(b), False          # taken by the first launch that reads scale / shift
-                    o.fin_fwd_op = (lib.rd_bn_finalize_fwd, (C.byref(b),))
-                else:
-                    self.fwd.append((lib.rd_gn_finalize_fwd if kind == 'gn' else lib.rd_bn_finalize_fwd, (C.byref(b),)))
-                if o.a_buf is not None:
-                    src = o.y_buf if o.up else o.buf
-                    Hh, Ww = (2 * H, 2 * W) if o.up else (H, W)
-                    self.fwd.append((lib.rd_bn_apply, (src.data_ptr(), None, o.a_buf.data_ptr(), o.scale.data_ptr(), None, o.shift.data_ptr(),
-                                                       self.slope, N, Hh, Ww, o.C, self.G, self.gs_arr, dt)))
-        # a folded forward finalize exists only inside the launch that TAKES it (_take_fwd_fin, as owner).  A BatchNorm site whose readers are
-        # all in other plans (flags 0), materialising passes or consumer kinds without a `fin` would otherwise never write its saved mean /
-        # invstd, running statistics and num_batches_tracked -- and the backward pass would read stale values: the explicit launch, at the end
-        for node in self.nodes:
-            o = node.out
-            if getattr(o, 'fin_fwd', None) is not None and o.plan is self and not o.fin_fwd_taken and self.fold_finalize != 2:
-                o.fin_fwd_taken = True
-                self.fwd.append(o.fin_fwd_op)
+                self._fwd_pool(node)
+            else:
+                self._fwd_conv(node)
+                if node.out.norm is not None:
+                    self._fwd_bn_site(node)
+        self._fwd_unclaimed_finalizes()
         if not self.training:
             return
-        # ---------------- backward, reverse order; bwd_split[m] = index where module m's backward starts
-        self.bwd_split, self.bwd_node_start = {}, {}
+        # backward, reverse order; bwd_split[m] = index where module m's backward starts
         for node in reversed(self.nodes):
-            if node.mname not in self.bwd_split:
-                self.bwd_split[node.mname] = len(self.bwd)
+            self.bwd_split.setdefault(node.mname, len(self.bwd))
             self.bwd_node_start[(node.mname, node.name)] = len(self.bwd)
-            o = node.out
-            H, W, N = o.H, o.W, o.N
             if isinstance(node, PoolNode):
-                a = node.src
-                has_bn = a.norm is not None
-                if has_bn or getattr(a, 'needs_grad', False):
-                    self.bwd.append((lib.rd_pool_bwd, (o.grad_buf().data_ptr(), a.buf.data_ptr(), a.scale.data_ptr() if has_bn else None,
-                                                       a.shift.data_ptr() if has_bn else None, self.slope if (has_bn and a.act) else 1.0,
-                                                       1 if (has_bn and a.act) else 0, a.grad_buf().data_ptr(), 1 if a.g_written else 0,
-                                                       a.plan.stat_ptr(a.bstats) if has_bn else None, N, H, W, o.C, self.G, self.gs_arr, dt, nsl),
-                                     dict(kernel='pool', what='bwd', layer='%s.%s' % (node.mname, node.name))))
-                    a.g_written = True
+                self._bwd_pool(node)
                 continue
-            if o.norm is not None:
-                q = L.RdBnBwd()
-                q.bstats = o.plan.stat_ptr(o.bstats)
-                q.mean, q.invstd = o.mean.data_ptr(), o.invstd.data_ptr()
-                q.P, q.Q, q.R = o.P.data_ptr(), o.Q.data_ptr(), o.R.data_ptr()
-                hw = (4 if o.up else 1) * H * W
-                for g in range(self.G):
-                    q.gamma[g] = o.norm.gamma_ptr(self, g, o.C)
-                    q.dgamma[g] = o.norm.grad_ptr(g, 'weight')
-                    q.dbeta[g] = o.norm.grad_ptr(g, 'bias')
-                    q.count[g] = float((self.gstart[g + 1] - self.gstart[g]) * hw)
-                q.C, q.G = o.C, self.G
-                if o.norm.kind == 'gn':                        # GroupNorm: the conv bias in front of it has a gradient (ramdsir.h)
-                    q.fstats = o.plan.stat_ptr(o.stats)
-                    q.conv_bias = None if o.up else self.bank.p(node.mname, node.name + '.bias').data_ptr()
-                    q.dbias = self.bank.g(node.mname, node.name + '.bias').data_ptr()
-                q.nslots = nsl
-                self.keep.append(q)
-                fin_op, fin_pos = (lib.rd_bn_finalize_bwd, (C.byref(q),)), len(self.bwd)
-                if self._folds(o, 'bwd') and not (o.up and o.plan.fold_finalize == 6):
-                    o.fin_bwd = self._fin_ptr(q)            # carried by rd_up_bwd, or by the gradient launch (owner) and the weight gradient
-                else:
-                    self.bwd.append((lib.rd_gn_finalize_bwd if o.norm.kind == 'gn' else lib.rd_bn_finalize_bwd, (C.byref(q),)))
-                # dz stored once: every >= 64-channel layer, and (round 4) a 32-channel layer whose gradient launch is 64-wide (more
-                # than 32 input channels: dec.convu1.conv1, rec.convu2.conv1) -- a BatchNorm-backward source keeps that launch on the
-                # two-operand conv_pf_kernel (110 us, the slowest gradient launch of the step); with a stored dz it runs on the
-                # persistent conv_ws_kernel like the other 64-wide gradients
-                wide_dgrad = self.materialize_dz_wide and isinstance(node, ConvNode) and node.taps == 9 and node.Cin > 32 and o.C >= 32
-                if (not o.up and self.materialize_dz_min_c is not None and (o.C >= self.materialize_dz_min_c or wide_dgrad)):
-                    o.dz_buf = self.alloc_act((N, H, W, o.C))
-                    self.bwd.append((lib.rd_bn_apply, (o.grad_buf().data_ptr(), o.buf.data_ptr(), o.dz_buf.data_ptr(), o.P.data_ptr(),
-                                                       o.Q.data_ptr(), o.R.data_ptr(), 1.0, N, H, W, o.C, self.G, self.gs_arr, dt)))
-                if o.up:
-                    o.dt_buf = self.alloc_act((N, H, W, o.C))
-                    fb = getattr(o, 'fin_bwd', None) if self.fold_finalize != 2 else None
-                    self.bwd.append((lib.rd_up_bwd, (o.grad_buf().data_ptr(), o.buf.data_ptr(), o.dt_buf.data_ptr(), o.P.data_ptr(),
-                                                     o.Q.data_ptr(), o.R.data_ptr(), N, H, W, o.C, self.G, self.gs_arr, dt,
-                                                     fb, L.FIN_OWNER if fb is not None else 0)))
-            # wgrad descriptor (launched below: fused with the dgrad where the pair qualifies)
-            wg = L.RdWgrad()
+            fin = self._bwd_bn_site(node) if node.out.norm is not None else None
+            wg, work = self._wgrad_desc(node)          # (before the gradient descriptor: their allocations keep this order)
+            p = self._dgrad_desc(node)
+            self._bwd_launches(node, p, wg, work, fin)
+
+    def _fwd_pool(self, node):
+        a, o = node.src, node.out
+        has_bn = a.norm is not None
+        fin, fin_flags = self._take_fwd_fin(a, 4) if has_bn else (None, 0)
+        self.fwd.append((L.lib().rd_pool_fwd, (a.buf.data_ptr(), a.scale.data_ptr() if has_bn else None, a.shift.data_ptr() if has_bn else None,
+                                               self.slope if (has_bn and a.act) else 1.0, o.buf.data_ptr(), o.N, o.H, o.W, o.C, self.G, self.gs_arr,
+                                               self.dt, fin, fin_flags),
+                         dict(kernel='pool', what='fwd', layer='%s.%s' % (node.mname, node.name))))
+
+    def _fwd_conv(self, node):
+        lib, dt, o = L.lib(), self.dt, node.out
+        p = L.RdConv()
+        p.cu_limit = self.conv_cus
+        p.stat_slots = self.nsl
+        small = node.Cin <= 32 and node.Cout <= 32
+        for i, (a, mode, n_off, g_fixed) in enumerate(node.inputs):
+            p.src[i] = self._src(a, mode, n_off, g_fixed, fold=1 if small else 2)
+        p.nsrc, p.taps = len(node.inputs), node.taps
+        p.w = self.wpack.ptr(node.mname, node.name, False)
+        p.bias = self.bank.p(node.mname, node.name + '.bias').data_ptr()
+        p.CinPad, p.CoutPad = self.wpack.pads(node.Cout, node.Cin)
+        p.N, p.H, p.W, p.Cin, p.Cout = o.N, o.H, o.W, node.Cin, node.Cout
+        p.G, p.gstart = self.G, self.gs_arr
+        p.emode, p.out = 0, o.buf.data_ptr()
+        p.stats = self.stat_ptr(o.stats) if (o.norm is not None and not o.up) else None
+        if ((self.store_operands & 1) and self.training and self.dtype == torch.bfloat16 and node.taps == 9 and node.Cin >= self.store_min_c
+                and lib.rd_conv_honours_src_out(C.byref(p), dt)):
             for i, (a, mode, n_off, g_fixed) in enumerate(node.inputs):
-                wg.a[i] = self._src(a, mode, n_off, g_fixed)
-                if getattr(node, 'a_store', None) and node.a_store[i] is not None:      # stored by the forward launch (rd_src_t.out)
-                    wg.a[i].ptr, wg.a[i].mode, wg.a[i].scale, wg.a[i].shift = node.a_store[i].data_ptr(), L.SRC_RAW, None, None
-            wg.na, wg.taps = len(node.inputs), node.taps
-            wg.dz = self._dz_src(node, owner=False)          # (promoted to owner below when the conv has no gradient launch)
-            wg.N, wg.H, wg.W, wg.Cin, wg.Cout = N, H, W, node.Cin, node.Cout
-            wg.G, wg.gstart = self.G, self.gs_arr
-            wg.dW = self.bank.g(node.mname, node.name + '.weight').data_ptr()
-            wg.beta = 0.0
-            wg.cu_limit = int(self.side_cus)
-            self.keep.append(wg)
-            node.wg = wg
-            # algorithmic work of the weight gradient (SURVEY.md 8d convention): the conv's logical input read once + the
-            # gradient w.r.t. its output read once (a BN-backward source is two tensors: g and the raw z); dW is negligible
-            esz = 2 if self.dtype == torch.bfloat16 else 4
-            dz_ops = 2 if wg.dz.mode == L.SRC_BNBWD else 1
-            dz_c = o.gCs if o.norm is None else o.C
-            wg_bytes, wg_flops = N * H * W * (node.Cin + dz_ops * dz_c) * esz, 2 * N * H * W * node.Cin * node.Cout * node.taps
-            # dgrad descriptor (none when no input needs a gradient, i.e. the first conv on the image)
-            dsts = []
-            for (a, mode, n_off, g_fixed) in node.inputs:
-                d = L.RdDst()
-                if mode == L.SRC_RAW and a.norm is None and not getattr(a, 'needs_grad', False):
-                    d.kind = L.DST_NONE
-                else:
-                    d.kind = {L.SRC_RAW: L.DST_PLAIN, L.SRC_AFF: L.DST_PLAIN, L.SRC_AFFACT: L.DST_PLAIN,
-                              L.SRC_POOL: L.DST_POOL, L.SRC_UP: L.DST_UPY}[mode]
-                    d.g = a.grad_buf().data_ptr()
-                    if d.kind == L.DST_UPY and a.y_buf is not None:
-                        d.kind = L.DST_PLAIN
-                    if a.norm is not None:
-                        d.z = (a.y_buf if (mode == L.SRC_UP and a.y_buf is not None) else a.buf).data_ptr()
-                        d.scale, d.shift = a.scale.data_ptr(), a.shift.data_ptr()
-                        d.bstats = a.plan.stat_ptr(a.bstats)
-                    d.act = 1 if (a.act and a.norm is not None) else 0
-                    d.accumulate = 1 if a.g_written else 0
-                    a.g_written = True
-                    d.Cd, d.slope, d.n_off, d.g_fixed = a.C, self.slope, n_off, g_fixed
-                    if a.norm is None and d.kind == L.DST_POOL:
-                        # the arg-max of the scatter needs the pooled values: the raw tensor under identity coefficients
-                        one, zero = self.unit_coef(a.C)
-                        d.z, d.scale, d.shift, d.slope, d.g_fixed = a.buf.data_ptr(), one.data_ptr(), zero.data_ptr(), 1.0, 0
-                dsts.append(d)
-            p = None
-            if not all(d.kind == L.DST_NONE for d in dsts):
-                p = L.RdConv()
-                p.cu_limit = int(self.conv_cus)
-                p.stat_slots = nsl
-                if not p.cu_limit and self.dgrad_cus and (node.Cin > 32 or node.Cout > 32):
-                    p.cu_limit = int(self.dgrad_cus)
-                p.src[0] = self._dz_src(node, owner=True)
-                p.nsrc, p.taps = 1, node.taps
-                p.w = wpack.ptr(node.mname, node.name, True)
-                p.bias = None
-                p.CinPad, p.CoutPad = wpack.pads(node.Cin, node.Cout)       # roles swapped: K = Cout, N = Cin
-                p.N, p.H, p.W, p.Cin, p.Cout = N, H, W, node.Cout, node.Cin
-                p.G, p.gstart = self.G, self.gs_arr
-                p.emode = 1
-                p.dst[0] = dsts[0]
-                if len(dsts) == 2:
-                    p.dst[1] = dsts[1]
-                    p.c_split = node.inputs[0][0].C
-                else:
-                    p.dst[1].kind = L.DST_NONE
-                    p.c_split = node.Cin
-                self.keep.append(p)
-            if p is None and wg.dz.fin:
-                wg.dz.fin_flags = L.FIN_OWNER                # the first conv on the image: its weight gradient is the only reader of P / Q / R
-            dmeta = self._conv_meta(node, N, H, W, node.Cout, node.Cin, 'dgrad') if p is not None else None
-            node.fused = bool(p is not None and self.fused_bwd and lib.rd_conv_bwd_fused_ok(C.byref(p), C.byref(wg), dt))
-            if self.fold_finalize in (5, 6) and not node.fused and not o.up and getattr(o, 'fin_bwd', None) is not None:
-                # fold_finalize 5 / 6: the backward finalize is folded only into launches that do gradient AND weight gradient at once
-                # (and, 5, into rd_up_bwd); a layer with two stand-alone launches keeps the explicit one in front of both
-                o.fin_bwd = None
-                wg.dz.fin, wg.dz.fin_flags = None, 0
-                if p is not None:
-                    p.src[0].fin, p.src[0].fin_flags = None, 0
-                assert fin_pos >= self.bwd_node_start[(node.mname, node.name)]      # inside this node's range: no recorded index moves
-                self.bwd.insert(fin_pos, fin_op)
-            dgrad_first = False
-            if node.fused:
-                # small-channel 3x3 conv: dgrad + weight gradient in ONE launch on the dgrad chain (csrc/conv_fused.hip: both are
-                # HBM-bound and read the same tensors); its per-workgroup dW sums are reduced on the weight-gradient lane, from a
-                # buffer of this layer's own (the next fused launch of the chain must not overwrite sums still to be reduced)
-                node.fused_ws = self.alloc_f32(max(lib.rd_conv_bwd_fused_workspace(C.byref(p), C.byref(wg), dt) // 4, 1))
-                wg.partial = node.fused_ws.data_ptr()
-                fmeta = dict(dmeta, kernel='conv_small_bwd_fused', what='dgrad+wgrad', bytes=dmeta['bytes'] + wg_bytes, flops=dmeta['flops'] + wg_flops)
-                self.bwd.append((lib.rd_conv_bwd_fused, (C.byref(p), C.byref(wg), dt), fmeta))
-                node.side_meta = [dict(kernel='wgrad_reduce', side=True, side_idx=0, layer='%s.%s' % (node.mname, node.name))]
-                self.bwd.append((lib.rd_conv_bwd_fused_reduce, (C.byref(p), C.byref(wg), dt), node.side_meta[0]))
+                if p.src[i].mode in (L.SRC_AFF, L.SRC_AFFACT):
+                    src_t = a.y_buf if (mode == L.SRC_UP and a.y_buf is not None) else a.buf
+                    node.a_store[i] = self.alloc_act(tuple(src_t.shape))
+                    p.src[i].out = node.a_store[i].data_ptr()
+        self.keep.append(p)
+        self.fwd.append((lib.rd_conv, (C.byref(p), dt), self._conv_meta(node, o.N, o.H, o.W, node.Cin, node.Cout, 'fwd')))
+
+    def _bn_groups(self, o, d):
+        """The per-group part shared by the two finalize descriptors (RdBnFwd / RdBnBwd) of BatchNorm site `o`."""
+        hw = (4 if o.up else 1) * o.H * o.W
+        for g in range(self.G):
+            d.gamma[g] = o.norm.gamma_ptr(self, g, o.C)
+            d.count[g] = float((self.gstart[g + 1] - self.gstart[g]) * hw)
+        d.C, d.G, d.nslots = o.C, self.G, self.nsl
+
+    def _fwd_bn_site(self, node):
+        """Behind a conv with a normalisation: [rd_up_stats], the finalize (folded into its first reader or launched), [rd_bn_apply]."""
+        lib, dt, o = L.lib(), self.dt, node.out
+        if o.up:
+            self.fwd.append((lib.rd_up_stats, (o.buf.data_ptr(), self.stat_ptr(o.stats), o.y_buf.data_ptr() if o.y_buf is not None else None,
+                                                o.N, o.H, o.W, o.C, self.G, self.gs_arr, dt, self.nsl)))
+        kind = o.norm.kind
+        if kind != 'bn' and any(self.gstart[g + 1] - self.gstart[g] != 1 for g in range(self.G)):
+            raise ValueError('norm=%r needs a launch plan with one statistics group per image (gstart = 0..N)' % kind)
+        b = L.RdBnFwd()
+        b.stats = self.stat_ptr(o.stats)
+        # the conv epilogues sum the result WITHOUT its bias; rd_up_stats sums y = up2(t) itself
+        b.conv_bias = None if o.up else self.bank.p(node.mname, node.name + '.bias').data_ptr()
+        b.scale, b.shift, b.mean, b.invstd = o.scale.data_ptr(), o.shift.data_ptr(), o.mean.data_ptr(), o.invstd.data_ptr()
+        self._bn_groups(o, b)
+        for g in range(self.G):
+            b.beta[g] = o.norm.beta_ptr(self, g, o.C)
+            b.running_mean[g] = o.norm.buf_ptr(g, 'running_mean')
+            b.running_var[g] = o.norm.buf_ptr(g, 'running_var')
+            b.num_batches_tracked[g] = o.norm.buf_ptr(g, 'num_batches_tracked')
+        # gn / in always normalise with the statistics of the input itself (nn.GroupNorm / nn.InstanceNorm2d in eval mode too)
+        b.eps, b.momentum, b.training = EPS, MOMENTUM, 1 if (self.training or kind != 'bn') else 0
+        self.keep.append(b)
+        if self.fold.fwd and self._can_fold(o):
+            if not self.fold.none:
+                o.fin_fwd, o.fin_fwd_op = C.addressof(b), (lib.rd_bn_finalize_fwd, (C.byref(b),))     # taken by the first launch that reads scale / shift
+        else:
+            self.fwd.append((lib.rd_gn_finalize_fwd if kind == 'gn' else lib.rd_bn_finalize_fwd, (C.byref(b),)))
+        if o.a_buf is not None:
+            src = o.y_buf if o.up else o.buf
+            Hh, Ww = (2 * o.H, 2 * o.W) if o.up else (o.H, o.W)
+            self.fwd.append((lib.rd_bn_apply, (src.data_ptr(), None, o.a_buf.data_ptr(), o.scale.data_ptr(), None, o.shift.data_ptr(),
+                                               self.slope, o.N, Hh, Ww, o.C, self.G, self.gs_arr, dt)))
+
+    def _fwd_unclaimed_finalizes(self):
+        """A folded forward finalize exists only inside the launch that TAKES it (_take_fwd_fin, as owner).  A BatchNorm site whose readers
+        are all in other plans (flags 0), materialising passes or consumer kinds without a `fin` would otherwise never write its saved
+        mean / invstd, running statistics and num_batches_tracked -- and the backward pass would read stale values: the explicit launch,
+        at the end."""
+        for node in self.nodes:
+            o = node.out
+            if o.fin_fwd is not None and o.plan is self and not o.fin_fwd_taken:
+                o.fin_fwd_taken = True
+                self.fwd.append(o.fin_fwd_op)
+
+    def _bwd_pool(self, node):
+        a, o = node.src, node.out
+        has_bn = a.norm is not None
+        if has_bn or a.needs_grad:
+            self.bwd.append((L.lib().rd_pool_bwd, (o.grad_buf().data_ptr(), a.buf.data_ptr(), a.scale.data_ptr() if has_bn else None,
+                                                   a.shift.data_ptr() if has_bn else None, self.slope if (has_bn and a.act) else 1.0,
+                                                   1 if (has_bn and a.act) else 0, a.grad_buf().data_ptr(), 1 if a.g_written else 0,
+                                                   a.plan.stat_ptr(a.bstats) if has_bn else None, o.N, o.H, o.W, o.C, self.G, self.gs_arr,
+                                                   self.dt, self.nsl),
+                             dict(kernel='pool', what='bwd', layer='%s.%s' % (node.mname, node.name))))
+            a.g_written = True
+
+    def _bwd_bn_site(self, node):
+        """In front of a normalised conv's gradient launches: the BatchNorm-backward finalize (folded into them or launched), [dz stored
+        once], [rd_up_bwd].  Returns (position, launch) of the explicit finalize where it was folded -- _bwd_launches may still un-fold it."""
+        lib, dt, o = L.lib(), self.dt, node.out
+        N, H, W = o.N, o.H, o.W
+        q = L.RdBnBwd()
+        q.bstats = self.stat_ptr(o.bstats)
+        q.mean, q.invstd = o.mean.data_ptr(), o.invstd.data_ptr()
+        q.P, q.Q, q.R = o.P.data_ptr(), o.Q.data_ptr(), o.R.data_ptr()
+        for g in range(self.G):
+            q.dgamma[g] = o.norm.grad_ptr(g, 'weight')
+            q.dbeta[g] = o.norm.grad_ptr(g, 'bias')
+        if o.norm.kind == 'gn':                        # GroupNorm: the conv bias in front of it has a gradient (ramdsir.h)
+            q.fstats = self.stat_ptr(o.stats)
+            q.conv_bias = None if o.up else self.bank.p(node.mname, node.name + '.bias').data_ptr()
+            q.dbias = self.bank.g(node.mname, node.name + '.bias').data_ptr()
+        self._bn_groups(o, q)
+        self.keep.append(q)
+        fin = None
+        if self._can_fold(o) and (self.fold.bwd_up if o.up else self.fold.bwd_fused):
+            if not self.fold.none:
+                o.fin_bwd = C.addressof(q)              # carried by rd_up_bwd, or by the gradient launch (owner) and the weight gradient
+                fin = (len(self.bwd), (lib.rd_bn_finalize_bwd, (C.byref(q),)))
+        else:
+            self.bwd.append((lib.rd_gn_finalize_bwd if o.norm.kind == 'gn' else lib.rd_bn_finalize_bwd, (C.byref(q),)))
+        # dz stored once: every >= 64-channel layer, and (round 4) a 32-channel layer whose gradient launch is 64-wide (more
+        # than 32 input channels: dec.convu1.conv1, rec.convu2.conv1) -- a BatchNorm-backward source keeps that launch on the
+        # two-operand conv_pf_kernel (110 us, the slowest gradient launch of the step); with a stored dz it runs on the
+        # persistent conv_ws_kernel like the other 64-wide gradients
+        wide_dgrad = self.materialize_dz_wide and node.taps == 9 and node.Cin > 32 and o.C >= 32
+        if not o.up and self.materialize_dz_min_c is not None and (o.C >= self.materialize_dz_min_c or wide_dgrad):
+            o.dz_buf = self.alloc_act((N, H, W, o.C))
+            self.bwd.append((lib.rd_bn_apply, (o.grad_buf().data_ptr(), o.buf.data_ptr(), o.dz_buf.data_ptr(), o.P.data_ptr(),
+                                               o.Q.data_ptr(), o.R.data_ptr(), 1.0, N, H, W, o.C, self.G, self.gs_arr, dt)))
+        if o.up:
+            o.dt_buf = self.alloc_act((N, H, W, o.C))
+            self.bwd.append((lib.rd_up_bwd, (o.grad_buf().data_ptr(), o.buf.data_ptr(), o.dt_buf.data_ptr(), o.P.data_ptr(),
+                                             o.Q.data_ptr(), o.R.data_ptr(), N, H, W, o.C, self.G, self.gs_arr, dt,
+                                             o.fin_bwd, L.FIN_OWNER if o.fin_bwd is not None else 0)))
+        return fin
+
+    def _wgrad_desc(self, node):
+        """The weight-gradient descriptor (launched by _bwd_launches: fused with the gradient where the pair qualifies) and its algorithmic
+        work (SURVEY.md 8d convention): the conv's logical input read once + the gradient w.r.t. its output read once (a BN-backward
+        source is two tensors: g and the raw z); dW is negligible."""
+        o = node.out
+        wg = L.RdWgrad()
+        for i, (a, mode, n_off, g_fixed) in enumerate(node.inputs):
+            wg.a[i] = self._src(a, mode, n_off, g_fixed)
+            if node.a_store[i] is not None:      # stored by the forward launch (rd_src_t.out)
+                wg.a[i].ptr, wg.a[i].mode, wg.a[i].scale, wg.a[i].shift = node.a_store[i].data_ptr(), L.SRC_RAW, None, None
+        wg.na, wg.taps = len(node.inputs), node.taps
+        wg.dz = self._dz_src(node, owner=False)          # (promoted to owner in _bwd_launches when the conv has no gradient launch)
+        wg.N, wg.H, wg.W, wg.Cin, wg.Cout = o.N, o.H, o.W, node.Cin, node.Cout
+        wg.G, wg.gstart = self.G, self.gs_arr
+        wg.dW = self.bank.g(node.mname, node.name + '.weight').data_ptr()
+        wg.beta = 0.0
+        wg.cu_limit = self.side_cus
+        self.keep.append(wg)
+        node.wg = wg
+        esz = 2 if self.dtype == torch.bfloat16 else 4
+        dz_ops = 2 if wg.dz.mode == L.SRC_BNBWD else 1
+        dz_c = o.gCs if o.norm is None else o.C
+        px = o.N * o.H * o.W
+        return wg, dict(bytes=px * (node.Cin + dz_ops * dz_c) * esz, flops=2 * px * node.Cin * node.Cout * node.taps)
+
+    def _dst(self, a, mode, n_off, g_fixed):
+        """Where a gradient launch's epilogue puts the gradient w.r.t. input `a` (read by the forward conv in `mode`)."""
+        d = L.RdDst()
+        if mode == L.SRC_RAW and a.norm is None and not a.needs_grad:
+            d.kind = L.DST_NONE
+            return d
+        d.kind = {L.SRC_RAW: L.DST_PLAIN, L.SRC_AFF: L.DST_PLAIN, L.SRC_AFFACT: L.DST_PLAIN,
+                  L.SRC_POOL: L.DST_POOL, L.SRC_UP: L.DST_UPY}[mode]
+        d.g = a.grad_buf().data_ptr()
+        if d.kind == L.DST_UPY and a.y_buf is not None:
+            d.kind = L.DST_PLAIN
+        if a.norm is not None:
+            d.z = (a.y_buf if (mode == L.SRC_UP and a.y_buf is not None) else a.buf).data_ptr()
+            d.scale, d.shift = a.scale.data_ptr(), a.shift.data_ptr()
+            d.bstats = a.plan.stat_ptr(a.bstats)
+        d.act = 1 if (a.act and a.norm is not None) else 0
+        d.accumulate = 1 if a.g_written else 0
+        a.g_written = True
+        d.Cd, d.slope, d.n_off, d.g_fixed = a.C, self.slope, n_off, g_fixed
+        if a.norm is None and d.kind == L.DST_POOL:
+            # the arg-max of the scatter needs the pooled values: the raw tensor under identity coefficients
+            one, zero = self.unit_coef(a.C)
+            d.z, d.scale, d.shift, d.slope, d.g_fixed = a.buf.data_ptr(), one.data_ptr(), zero.data_ptr(), 1.0, 0
+        return d
+
+    def _dgrad_desc(self, node):
+        """The gradient-launch descriptor; None when no input needs a gradient (the first conv on the image)."""
+        o = node.out
+        dsts = [self._dst(*inp) for inp in node.inputs]
+        if all(d.kind == L.DST_NONE for d in dsts):
+            return None
+        p = L.RdConv()
+        p.cu_limit = self.conv_cus
+        p.stat_slots = self.nsl
+        if not p.cu_limit and self.dgrad_cus and (node.Cin > 32 or node.Cout > 32):
+            p.cu_limit = self.dgrad_cus
+        p.src[0] = self._dz_src(node, owner=True)
+        p.nsrc, p.taps = 1, node.taps
+        p.w = self.wpack.ptr(node.mname, node.name, True)
+        p.bias = None
+        p.CinPad, p.CoutPad = self.wpack.pads(node.Cin, node.Cout)       # roles swapped: K = Cout, N = Cin
+        p.N, p.H, p.W, p.Cin, p.Cout = o.N, o.H, o.W, node.Cout, node.Cin
+        p.G, p.gstart = self.G, self.gs_arr
+        p.emode = 1
+        p.dst[0] = dsts[0]
+        if len(dsts) == 2:
+            p.dst[1] = dsts[1]
+            p.c_split = node.inputs[0][0].C
+        else:
+            p.dst[1].kind = L.DST_NONE
+            p.c_split = node.Cin
+        self.keep.append(p)
+        return p
+
+    def _bwd_launches(self, node, p, wg, work, fin):
+        """The launch order of one conv's backward: the fused pair; or the weight gradient (side lane) in front of the gradient launch,
+        behind it where it reads what that launch stores or derives; then the bias column sum (output convs)."""
+        lib, dt, o = L.lib(), self.dt, node.out
+        if p is None and wg.dz.fin:
+            wg.dz.fin_flags = L.FIN_OWNER                # the first conv on the image: its weight gradient is the only reader of P / Q / R
+        dmeta = self._conv_meta(node, o.N, o.H, o.W, node.Cout, node.Cin, 'dgrad') if p is not None else None
+        node.fused = bool(p is not None and self.fused_bwd and lib.rd_conv_bwd_fused_ok(C.byref(p), C.byref(wg), dt))
+        if fin is not None and not (node.fused or o.up or self.fold.bwd_pair):
+            # the backward finalize is folded only into launches that do gradient AND weight gradient at once (and into rd_up_bwd); a
+            # layer with two stand-alone launches keeps the explicit one in front of both
+            o.fin_bwd = None
+            wg.dz.fin, wg.dz.fin_flags = None, 0
+            if p is not None:
+                p.src[0].fin, p.src[0].fin_flags = None, 0
+            assert fin[0] >= self.bwd_node_start[(node.mname, node.name)]      # inside this node's range: no recorded index moves
+            self.bwd.insert(*fin)
+        if node.fused:
+            self._launch_fused_pair(node, p, wg, dmeta, work)
+            dgrad_done = True
+        else:
+            dgrad_done = self._launch_dgrad_ahead(node, p, wg, dmeta)
+            self.ws_bytes = max(self.ws_bytes, lib.rd_wgrad_workspace(C.byref(wg), dt))      # (the unfused weight gradients only)
+            node.side_meta = [dict(kernel='wgrad', side=True, side_idx=0, layer='%s.%s' % (node.mname, node.name), **work)]
+            self.bwd.append((lib.rd_wgrad, (C.byref(wg), dt), node.side_meta[0]))
+        if node.has_bias_grad:
+            node.bias_ws = self.alloc_f32(8192)
+            node.side_meta.append(dict(kernel='colsum', side=True, side_idx=0))
+            self.bwd.append((lib.rd_colsum, (o.grad_buf().data_ptr(), self.bank.g(node.mname, node.name + '.bias').data_ptr(),
+                                             node.bias_ws.data_ptr(), o.N * o.H * o.W, o.C, o.gCs, 0.0, dt), node.side_meta[-1]))
+        if p is not None and not dgrad_done:
+            halves = self._dgrad_halves(p) if self.split_wide_dgrad else None
+            if halves is not None:
+                hmeta = dict(dmeta, kernel='conv_small_kernel<bf16,%d,*>' % p.taps, bytes=dmeta['bytes'] // 2, flops=dmeta['flops'] // 2)
+                for q in halves:
+                    self.bwd.append((lib.rd_conv, (C.byref(q), dt), dict(hmeta)))
             else:
-                # the gradient launch stores the dz its loader forms (rd_src_t.out) and the weight gradient, enqueued BEHIND it, reads that
-                dgrad_first = bool(p is not None and (self.store_operands & 2) and self.dtype == torch.bfloat16 and p.src[0].mode == L.SRC_BNBWD and node.Cout >= self.store_min_c
-                                   and not self.split_wide_dgrad and lib.rd_conv_honours_src_out(C.byref(p), dt))
-                # a folded BatchNorm-backward finalize (fold_wgrad_order 1): the gradient launch derives P / Q / R as the owner and the weight
-                # gradient, enqueued BEHIND it, reads them like any later launch -- instead of repeating the prologue on its own lane
-                fold_first = bool(p is not None and not dgrad_first and p.src[0].fin and self.fold_wgrad_behind and node is not self.nodes[0])   # (the
-                # plan's LAST gradient launch stays last: TrainStep moves the restoration decoder's to the main lane, behind the join)
-                if fold_first:
-                    wg.dz.fin, wg.dz.fin_flags = None, 0
-                    self.bwd.append((lib.rd_conv, (C.byref(p), dt), dmeta))
-                    dgrad_first = True
-                elif dgrad_first:
-                    o.dz_store = self.alloc_act((N, H, W, o.C))
-                    p.src[0].out = o.dz_store.data_ptr()
-                    wg.dz.ptr, wg.dz.ptr2, wg.dz.mode = o.dz_store.data_ptr(), None, L.SRC_RAW
-                    wg.dz.scale = wg.dz.shift = wg.dz.q = None
-                    wg.dz.fin, wg.dz.fin_flags = None, 0
-                    self.bwd.append((lib.rd_conv, (C.byref(p), dt), dmeta))
-                ws_need = max(ws_need, lib.rd_wgrad_workspace(C.byref(wg), dt))
-                node.side_meta = [dict(kernel='wgrad', side=True, side_idx=0, layer='%s.%s' % (node.mname, node.name), bytes=wg_bytes, flops=wg_flops)]
-                self.bwd.append((lib.rd_wgrad, (C.byref(wg), dt), node.side_meta[0]))
-            if node.has_bias_grad:
-                node.bias_ws = self.alloc_f32(8192)
-                node.side_meta.append(dict(kernel='colsum', side=True, side_idx=0))
-                self.bwd.append((lib.rd_colsum, (o.grad_buf().data_ptr(), self.bank.g(node.mname, node.name + '.bias').data_ptr(),
-                                                 node.bias_ws.data_ptr(), N * H * W, o.C, o.gCs, 0.0, dt), node.side_meta[-1]))
-            if p is not None and not node.fused and not dgrad_first:
-                halves = self._dgrad_halves(p) if self.split_wide_dgrad else None
-                if halves is not None:
-                    for q in halves:
-                        self.bwd.append((lib.rd_conv, (C.byref(q), dt), dict(dmeta, kernel='conv_small_kernel<bf16,%d,*>' % p.taps, bytes=dmeta['bytes'] // 2,
-                                                                               flops=dmeta['flops'] // 2)))
-                else:
-                    self.bwd.append((lib.rd_conv, (C.byref(p), dt), dmeta))
-        self.ws_bytes = ws_need
+                self.bwd.append((lib.rd_conv, (C.byref(p), dt), dmeta))
+
+    def _launch_fused_pair(self, node, p, wg, dmeta, work):
+        """Small-channel 3x3 conv: dgrad + weight gradient in ONE launch on the dgrad chain (csrc/conv_fused.hip: both are HBM-bound and
+        read the same tensors); its per-workgroup dW sums are reduced on the weight-gradient lane, from a buffer of this layer's own
+        (the next fused launch of the chain must not overwrite sums still to be reduced)."""
+        lib, dt = L.lib(), self.dt
+        node.fused_ws = self.alloc_f32(max(lib.rd_conv_bwd_fused_workspace(C.byref(p), C.byref(wg), dt) // 4, 1))
+        wg.partial = node.fused_ws.data_ptr()
+        fmeta = dict(dmeta, kernel='conv_small_bwd_fused', what='dgrad+wgrad', bytes=dmeta['bytes'] + work['bytes'], flops=dmeta['flops'] + work['flops'])
+        self.bwd.append((lib.rd_conv_bwd_fused, (C.byref(p), C.byref(wg), dt), fmeta))
+        node.side_meta = [dict(kernel='wgrad_reduce', side=True, side_idx=0, layer='%s.%s' % (node.mname, node.name))]
+        self.bwd.append((lib.rd_conv_bwd_fused_reduce, (C.byref(p), C.byref(wg), dt), node.side_meta[0]))
+
+    def _launch_dgrad_ahead(self, node, p, wg, dmeta):
+        """Enqueue the gradient launch IN FRONT of the layer's stand-alone weight gradient where the latter reads what it leaves behind;
+        returns whether it did.  Two cases:
+          * the gradient launch stores the dz its loader forms (rd_src_t.out) and the weight gradient reads that;
+          * fold_wgrad_behind, with a folded BatchNorm-backward finalize: the gradient launch derives P / Q / R as the owner and the weight
+            gradient reads them like any later launch -- instead of repeating the prologue on its own lane.  Not for the plan's LAST
+            gradient launch, which stays last: TrainStep moves the restoration decoder's to the main lane, behind the join."""
+        lib, dt, o = L.lib(), self.dt, node.out
+        if p is None:
+            return False
+        stores_dz = bool((self.store_operands & 2) and self.dtype == torch.bfloat16 and p.src[0].mode == L.SRC_BNBWD and node.Cout >= self.store_min_c
+                         and not self.split_wide_dgrad and lib.rd_conv_honours_src_out(C.byref(p), dt))
+        if stores_dz:
+            o.dz_store = self.alloc_act((o.N, o.H, o.W, o.C))
+            p.src[0].out = o.dz_store.data_ptr()
+            wg.dz.ptr, wg.dz.ptr2, wg.dz.mode = o.dz_store.data_ptr(), None, L.SRC_RAW
+            wg.dz.scale = wg.dz.shift = wg.dz.q = None
+        elif not (p.src[0].fin and self.fold_wgrad_behind and node is not self.nodes[0]):
+            return False
+        wg.dz.fin, wg.dz.fin_flags = None, 0
+        self.bwd.append((lib.rd_conv, (C.byref(p), dt), dmeta))
+        return True
 
     def _dgrad_halves(self, p):
         """A gradient launch with ONE input chunk (<= 32 channels of dz) and 33..64 output channels into one plain tensor -- in the
@@ -820,8 +901,8 @@ class Plan:
         wss = list(ws) if isinstance(ws, (list, tuple)) else [ws]
         k = 0
         for node in reversed(self.nodes):                 # backward order = launch order
-            if hasattr(node, 'wg'):
-                if not getattr(node, 'fused', False):            # fused layers keep their own per-layer buffer
+            if node.wg is not None:
+                if not node.fused:            # fused layers keep their own per-layer buffer
                     node.wg.partial = wss[k % len(wss)].data_ptr()
                 for m in node.side_meta:
                     m['side_idx'] = k % len(wss)

@@ -35,24 +35,13 @@ class TrainStep:
         self.wpack = wpack if wpack is not None else E.WeightPack(bank, mods, dtype)
         # ---- graphs
         self.opt = opt = T.options(options)
-        self.seg = E.Plan(bank, dtype, 2 * B, [0, B, 2 * B], slope=slope)
-        self.seg.pad_narrow = True
-        self.seg.materialize_up = bool(opt['up_mat'])
-        self.seg.materialize_pool = bool(opt['pool_mat'])
-        self.seg.fused_bwd = bool(opt['fused_bwd'])
-        self.seg.fold_finalize = int(opt['fold_finalize'])
-        self.seg.fold_wgrad_behind = bool(opt['fold_wgrad_behind'])
-        self.seg.fold_fwd_kinds = int(opt['fold_fwd_kinds'])
-        self.seg.store_operands = int(opt['store_wgrad_operands'])
-        self.seg.store_min_c = int(opt['store_wgrad_min_c'])
         # lane budgets are tuned for the bf16 kernels (in fp32 the weight gradients are several times heavier and the side lane
         # itself becomes the critical path when it is narrowed: 315 -> 268 images/s)
         budget = bool(opt['fork']) and dtype == torch.bfloat16
-        self.seg.side_cus = T.cu_budget(opt['side_cus'], dev) if budget else 0
-        self.seg.dgrad_cus = T.cu_budget(opt['dgrad_cus'], dev) if budget else 0
-        self.seg.materialize_min_c = opt['mat_min_c'] if opt['mat_min_c'] > 0 else None
-        self.seg.materialize_dz_min_c = opt['mat_dz_min_c'] if opt['mat_dz_min_c'] > 0 else None
-        self.seg.materialize_dz_wide = bool(opt['mat_dz_wide'])
+        lane = bool(budget and opt['rec_lane'])
+        cus = lambda key, on: T.cu_budget(opt[key], dev) if on else 0
+        self.seg = E.Plan(bank, dtype, 2 * B, [0, B, 2 * B], slope=slope, options=opt, fused_step=True, pad_narrow=True,
+                          side_cus=cus('side_cus', budget), dgrad_cus=cus('dgrad_cus', budget))
         slot = self.seg.slot_channels()
         self.x = E.Act(self.seg, 2 * B, H, W, in_channels, name='input', cstride=slot if in_channels < slot else None)
         self.feats = E.build_encoder(self.seg, self.x, n=n)
@@ -60,22 +49,8 @@ class TrainStep:
         gs = [0]
         for b in batch_sizes:
             gs.append(gs[-1] + b)
-        self.rec = E.Plan(bank, dtype, B, gs, slope=slope)
-        self.rec.pad_narrow = True
-        self.rec.materialize_up = self.seg.materialize_up
-        self.rec.materialize_pool = self.seg.materialize_pool
-        self.rec.fused_bwd = self.seg.fused_bwd
-        self.rec.fold_finalize = self.seg.fold_finalize
-        self.rec.fold_wgrad_behind = self.seg.fold_wgrad_behind
-        self.rec.fold_fwd_kinds = self.seg.fold_fwd_kinds
-        self.rec.store_operands = self.seg.store_operands
-        self.rec.store_min_c = self.seg.store_min_c
-        lane = bool(budget and opt['rec_lane'])
-        self.rec.side_cus = T.cu_budget(opt['rec_cus'], dev) if lane else 0    # its weight gradients run inline on its own lane
-        self.rec.conv_cus = T.cu_budget(opt['rec_cus'], dev) if lane else 0
-        self.rec.materialize_min_c = self.seg.materialize_min_c
-        self.rec.materialize_dz_min_c = self.seg.materialize_dz_min_c
-        self.rec.materialize_dz_wide = self.seg.materialize_dz_wide
+        self.rec = E.Plan(bank, dtype, B, gs, slope=slope, options=opt, fused_step=True, pad_narrow=True,
+                          side_cus=cus('rec_cus', lane), conv_cus=cus('rec_cus', lane))    # its weight gradients run inline on its own lane
         self.rec_logits = E.build_rec_decoder(self.rec, self.feats[4], n_off=B, g_fixed=1, domains=list(range(len(batch_sizes))),
                                               n=n, num_classes=in_channels)
         self.seg.build(self.wpack)

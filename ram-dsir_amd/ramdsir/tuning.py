@@ -10,7 +10,7 @@ DEFAULTS = dict(
                           # round 4: conv_ws_kernel<2,TS,true> computes dz from (z, g) in its loader warps, so the gradient launch and the
                           # weight gradient both read the two operands and the extra pass (14 launches, 0.25 ms of main-lane time) is gone:
                           # 4.36 -> 4.23 ms/step together with side_cus 128 -> 96 (docs/experiments.md, round-4 rows)
-    mat_dz_wide=True,     # with mat_dz_min_c > 0: ... and for a 32-channel layer whose gradient launch is 64-wide (engine.Plan.build)
+    mat_dz_wide=True,     # with mat_dz_min_c > 0: ... and for a 32-channel layer whose gradient launch is 64-wide (engine.Plan._bwd_bn_site)
     up_mat=True,          # store y = up2(t) once (rd_up_stats) instead of interpolating t in the loaders of the 3x3 conv behind it (round 5: 4.19 vs
                           # 5.0+ ms/step, docs/experiments.md)
     pool_mat=True,        # store the 2x2 max-pool in front of ConvD levels 2-5 once (rd_pool_fwd / rd_pool_bwd)
@@ -52,7 +52,8 @@ DEFAULTS = dict(
     fold_finalize=6,      # BatchNorm finalize launches folded into the prologue of the launch that first reads the coefficients (rd_src_t.fin,
                           # csrc/bn_fin.h; statistic sums over 8 slot copies instead of 64).  0: explicit launches; 1: all 76 of the step;
                           # 3: the forward ones; 4: the backward ones; 6 (default): the forward ones + the backward ones of layers whose
-                          # gradient and weight gradient are ONE launch; 5: 6 + rd_up_bwd; 2: timing experiment, no finalize at all.
+                          # gradient and weight gradient are ONE launch; 5: 6 + rd_up_bwd; 2: timing experiment, no finalize at all
+                          # (decoded into named facts by the table engine.FOLD_FINALIZE).
                           # Same box, alternating (scripts/options_ab.py): explicit 4.267, 6: 4.147 ms/step; 1: 4.230 against 4.213 and
                           # 3: 4.161 -- a stand-alone weight gradient beside its gradient launch repeats the prologue on its own lane,
                           # and the many-workgroup rd_up_bwd pays it per workgroup; without ANY finalize the step takes 4.03.  Also measured:
