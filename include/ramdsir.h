@@ -186,6 +186,27 @@ int64_t rd_conv_bwd_fused_workspace(const rd_conv_t* dgrad, const rd_wgrad_t* wg
 int rd_conv_bwd_fused(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype, void* stream);
 int rd_conv_bwd_fused_reduce(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype, void* stream);
 
+/* Routing queries: what rd_conv / rd_wgrad / rd_conv_bwd_fused(_reduce) WOULD launch for a descriptor, from the same host function
+ * the entry points launch from.  Pure host arithmetic on the descriptor and the device's compute-unit count: nothing is launched and
+ * no data pointer is dereferenced (only pointer VALUES are looked at, for the alignment rules; rd_src_t.fin is not read).
+ * `kernel` is the instantiation as spelled in the source (static storage), e.g. "conv_ws_kernel<1, 1, false, true>"; iarg holds the
+ * integer kernel arguments the dispatcher computes, in the kernel's argument order, 0 beyond them:
+ *   conv kernels {tiles_total | arg | tiles_per_wg};  weight-gradient kernels {CoutPadW, CinPadW, total_tiles};
+ *   the split reduction {nsplit, taps, Cout, Cin, CoutPadW, CinPadW};  the fused backward {tiles_per_wg}. */
+typedef struct {
+    const char* kernel;
+    int32_t grid[3], block, lds;
+    int32_t iarg[6];
+    int32_t stores_sources;  /* rd_conv only: the launch honours rd_src_t.out, i.e. writes the out tensors it is given (this is
+                              * what rd_conv_honours_src_out returns; the storing instantiation is chosen when a source asks) */
+} rd_route_t;
+/* rd_conv's own return code for the descriptor (-1 / -2); 0: *out is what rd_conv would launch */
+int rd_conv_route(const rd_conv_t* p, int dtype, rd_route_t* out);
+/* the number of launches (the weight-gradient kernel, then its split reduction), or rd_wgrad's return code (< 0) */
+int rd_wgrad_route(const rd_wgrad_t* p, int dtype, rd_route_t out[2]);
+/* 2: out[0] is rd_conv_bwd_fused's launch, out[1] rd_conv_bwd_fused_reduce's; -1 when the pair does not qualify */
+int rd_conv_bwd_fused_route(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype, rd_route_t out[2]);
+
 /* rd_pack_weights: OIHW fp32 master weights -> the packed operand rd_conv reads.
  * K-chunk-major, CK = 32 (bf16) / 16 (fp32) input channels = the 64 bytes one K step of rd_conv consumes:
  * transpose=0: forward  [CinPad/CK][tap][CoutPad][CK]  (tap = kh*3+kw)

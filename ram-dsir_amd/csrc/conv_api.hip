@@ -118,65 +118,128 @@ int rd_pack_weights_batched(const float* params, void* packed, const rd_pack_ent
     return (int)hipGetLastError();
 }
 
-int rd_conv(const rd_conv_t* p, int dtype, void* stream) {
+// ---- rd_conv: validate -> route -> launch.  conv_validate() is rd_conv's return code for the descriptor; conv_route() is THE place that
+// lists the order in which the kernel families are asked (conv_dispatch.h says which file each lives in).  It launches nothing.
+static int conv_validate(const rd_conv_t* p, int dtype) {
     if (!p || (p->taps != 9 && p->taps != 1) || p->G < 1 || p->G > RD_MAX_GROUPS || p->nsrc < 1 || p->nsrc > 2) return -1;
     const int ck = dtype == RD_BF16 ? 32 : 16;
     if (p->CinPad % ck || p->CoutPad % 32 || p->CinPad < p->Cin || p->CoutPad < p->Cout) return -2;
-    hipStream_t st = (hipStream_t)stream;
     if (p->stat_slots < 0 || p->stat_slots > RD_STAT_SLOTS) return -2;               // the kernels add into slot (index mod stat_slots) of [RD_STAT_SLOTS] copies
-    if (rdfin::make_arg(rdfin::current(), p->src, p->nsrc)) return -3;                // rd_src_t.fin: copied into the kernel arguments
     if (p->w_tap_rows && !(p->CinPad == ck && p->CoutPad == 32 && p->emode == 1 && p->w_tap_rows >= p->CoutPad)) return -2;   // ramdsir.h
-    if (p->CinPad == ck && p->CoutPad == 32) return rd_conv_small_dispatch(*p, dtype, st);   // one K chunk, one N block
-    return rd_conv_big_dispatch(*p, dtype, st);
+    return 0;
+}
+
+static void conv_route(const rd_conv_t& p, int dtype, Route& r) {
+    if (p.CinPad == (dtype == RD_BF16 ? 32 : 16) && p.CoutPad == 32) {               // one K chunk, one N block
+        if (!rd_route_small_fwd(p, dtype, r)) rd_route_small(p, dtype, r);
+        return;
+    }
+    const bool bf16 = dtype == RD_BF16, nb2 = rd_conv_nb2(p, dtype);
+    if (bf16 && nb2 && (rd_route_ws(p, r) || rd_route_pp(p, r))) return;              // 3x3 with 64-channel tiles, persistent
+    if (bf16 && rd_route_pf_lean(p, nb2, r)) return;                                  // chunk-pipelined, register epilogue
+    if (rd_route_pf(p, dtype, nb2, r)) return;                                        // chunk-pipelined, LDS-staged epilogue
+    rd_route_conv_kernel(p, dtype, nb2, r);
+}
+
+int rd_conv(const rd_conv_t* p, int dtype, void* stream) {
+    if (const int rc = conv_validate(p, dtype)) return rc;
+    if (rdfin::make_arg(rdfin::current(), p->src, p->nsrc)) return -3;                // rd_src_t.fin: copied into the kernel arguments
+    Route r;
+    conv_route(*p, dtype, r);
+    return rd_route_launch(r, p, nullptr, (hipStream_t)stream);
+}
+
+int rd_conv_route(const rd_conv_t* p, int dtype, rd_route_t* out) {
+    if (const int rc = conv_validate(p, dtype)) return rc;
+    Route r;
+    conv_route(*p, dtype, r);
+    *out = r.v;
+    return 0;
 }
 
 int rd_conv_honours_src_out(const rd_conv_t* p, int dtype) {
-    if (!p || (p->taps != 9 && p->taps != 1) || p->G < 1 || p->G > RD_MAX_GROUPS || p->nsrc < 1 || p->nsrc > 2) return 0;
-    const int ck = dtype == RD_BF16 ? 32 : 16;
-    if (p->CinPad % ck || p->CoutPad % 32 || p->CinPad < p->Cin || p->CoutPad < p->Cout || p->w_tap_rows) return 0;
-    if (p->CinPad == ck && p->CoutPad == 32) return 0;           // the small-channel kernels
-    return rd_conv_big_stores_sources(*p, dtype) ? 1 : 0;
+    rd_route_t v;
+    return rd_conv_route(p, dtype, &v) == 0 && v.stores_sources;
+}
+
+// ---- rd_wgrad: the route's first record is the weight-gradient kernel, the second its split reduction (wgrad.hip)
+static int wgrad_validate(const rd_wgrad_t* p) {
+    if (!p || (p->taps != 9 && p->taps != 1) || p->G < 1 || p->G > RD_MAX_GROUPS || p->na < 1 || p->na > 2) return -1;
+    if (p->a[0].fin || (p->na > 1 && p->a[1].fin)) return -3;                         // only dz may carry a folded finalize (ramdsir.h)
+    return 0;
+}
+
+int rd_wgrad_route(const rd_wgrad_t* p, int dtype, rd_route_t out[2]) {
+    if (const int rc = wgrad_validate(p)) return rc;
+    Route r[2];
+    const int n = rd_wgrad_route_plan(*p, dtype, r);
+    for (int i = 0; i < n; ++i) out[i] = r[i].v;
+    return n;
 }
 
 int64_t rd_wgrad_workspace(const rd_wgrad_t* p, int dtype) {
-    return rd_wgrad_ws_bytes(*p, dtype);
+    Route r[2];
+    rd_wgrad_route_plan(*p, dtype, r);                                                // partial[nsplit = grid.x][taps][CoutPadW][CinPadW]
+    return (int64_t)r[0].v.grid[0] * p->taps * r[0].v.iarg[0] * r[0].v.iarg[1] * (int64_t)sizeof(float);
 }
 
 int rd_wgrad(const rd_wgrad_t* p, int dtype, void* stream) {
-    if (!p || (p->taps != 9 && p->taps != 1) || p->G < 1 || p->G > RD_MAX_GROUPS || p->na < 1 || p->na > 2) return -1;
-    if (p->a[0].fin || (p->na > 1 && p->a[1].fin)) return -3;                         // only dz may carry a folded finalize (ramdsir.h)
+    if (const int rc = wgrad_validate(p)) return rc;
     if (rdfin::make_arg(rdfin::current(), &p->dz, 1)) return -3;
-    return rd_wgrad_dispatch(*p, dtype, (hipStream_t)stream);
+    Route r[2];
+    const int n = rd_wgrad_route_plan(*p, dtype, r);
+    for (int i = 0; i < n; ++i)
+        if (const int e = rd_route_launch(r[i], p, nullptr, (hipStream_t)stream)) return e;
+    return 0;
 }
 
 int rd_wgrad_reduce(const float* partial, float* dW, int nsplit, int taps, int Cout, int Cin, int CoutPadW, int CinPadW, float beta,
                     void* stream) {
     if (!partial || !dW || nsplit < 1 || taps < 1 || Cout < 1 || Cin < 1 || CoutPadW < Cout || CinPadW < Cin || CinPadW % 16) return -1;
-    return rd_wgrad_reduce_launch(partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta, (hipStream_t)stream);
+    rd_wgrad_t w = {};
+    w.partial = const_cast<float*>(partial);
+    w.dW = dW;
+    w.beta = beta;
+    Route r;
+    rd_route_wgrad_reduce(partial, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, r);
+    return rd_route_launch(r, &w, nullptr, (hipStream_t)stream);
 }
 
-// ---- backward of a small-channel 3x3 conv in one launch (conv_fused.hip)
+// ---- backward of a small-channel 3x3 conv in one launch (conv_fused.hip): route[0] the fused kernel, route[1] its split reduction
 int rd_conv_bwd_fused_ok(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype) {
     if (!dgrad || !wgrad || dgrad->G < 1 || dgrad->G > RD_MAX_GROUPS) return 0;
     return rd_bwd_fused_ok(*dgrad, *wgrad, dtype) ? 1 : 0;
 }
 
+int rd_conv_bwd_fused_route(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype, rd_route_t out[2]) {
+    if (!rd_conv_bwd_fused_ok(dgrad, wgrad, dtype)) return -1;
+    Route r[2];
+    rd_bwd_fused_route(*dgrad, *wgrad, r);
+    out[0] = r[0].v;
+    out[1] = r[1].v;
+    return 2;
+}
+
 int64_t rd_conv_bwd_fused_workspace(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype) {
-    if (!rd_conv_bwd_fused_ok(dgrad, wgrad, dtype)) return 0;
-    return rd_bwd_fused_ws_bytes(*dgrad, *wgrad);
+    rd_route_t v[2];
+    if (rd_conv_bwd_fused_route(dgrad, wgrad, dtype, v) < 0) return 0;
+    return (int64_t)v[1].iarg[0] * v[1].iarg[1] * v[1].iarg[4] * v[1].iarg[5] * (int64_t)sizeof(float);   // the reduction's nsplit x taps x pads
 }
 
 int rd_conv_bwd_fused(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype, void* stream) {
     if (!rd_conv_bwd_fused_ok(dgrad, wgrad, dtype) || !wgrad->partial || !wgrad->dW) return -1;
     if (dgrad->stat_slots < 0 || dgrad->stat_slots > RD_STAT_SLOTS) return -2;
     if (rdfin::make_arg(rdfin::current(), dgrad->src, dgrad->nsrc)) return -3;          // the gradient descriptor's dz carries it; wgrad->dz.fin is ignored
-    return rd_bwd_fused_dispatch(*dgrad, *wgrad, (hipStream_t)stream);
+    Route r[2];
+    rd_bwd_fused_route(*dgrad, *wgrad, r);
+    return rd_route_launch(r[0], dgrad, wgrad, (hipStream_t)stream);
 }
 
 int rd_conv_bwd_fused_reduce(const rd_conv_t* dgrad, const rd_wgrad_t* wgrad, int dtype, void* stream) {
     if (!rd_conv_bwd_fused_ok(dgrad, wgrad, dtype) || !wgrad->partial || !wgrad->dW) return -1;
-    return rd_bwd_fused_reduce_dispatch(*dgrad, *wgrad, (hipStream_t)stream);
+    Route r[2];
+    rd_bwd_fused_route(*dgrad, *wgrad, r);
+    return rd_route_launch(r[1], wgrad, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"
-

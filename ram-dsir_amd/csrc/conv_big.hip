@@ -99,57 +99,26 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const rd_conv_t p, const r
     conv_epilogue<T, NB>(p, acc, smem, tid, n, g, y0, x0, n0, slot);
 }
 
-template <typename T, int TAPS, int NB>
-int launch_conv(const rd_conv_t& p, hipStream_t st) {
-    constexpr int HALO = (TAPS == 9) ? 1 : 0;
-    constexpr int PH = TH + 2 * HALO, PW = TW + 2 * HALO;
-    const size_t lds = conv_pf_lds<TAPS, NB>(p);
-    dim3 grid(((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH), p.CoutPad / (NB * 32), p.N);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_kernel<T, TAPS, NB>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        attr_set = true;
-    }
-    if constexpr (sizeof(T) == 2 && TAPS == 9 && NB == 2) {
-        static const bool pp_off = rd_switch("RD_CONV_PP_OFF", 0) != 0;
-        if (!pp_off) {
-            const int rc = rd_conv_pp_dispatch(p, st);
-            if (rc != RD_CONV_PP_NA) return rc;
-        }
-    }
-    if constexpr (sizeof(T) == 2) {
-        static const bool lean_off = rd_switch("RD_CONV_PF_LEAN_OFF", 0) != 0;
-        if (!lean_off && rd_switch("RD_CONV_PF_OFF", 0) == 0) {
-            const int rc = rd_conv_pf_lean_dispatch(p, NB == 2, st);      // register epilogues (conv_lean.hip)
-            if (rc != RD_CONV_PP_NA) return rc;
-        }
-    }
-    if constexpr (sizeof(T) == 2) {
-        static const bool pf_off = rd_switch("RD_CONV_PF_OFF", 0) != 0;
-        const int nq = conv_pf_kind(p);
-        if (!pf_off && nq && lds <= (size_t)72 * 1024) {
-            static bool attr_pf = false;
-            if (!attr_pf) {
-                const int lds_max = 72 * 1024;                  // two workgroups per CU; covers CinPad <= 1024
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pf_kernel<T, TAPS, NB, 1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pf_kernel<T, TAPS, NB, 2>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-                attr_pf = true;
-            }
-            if (nq == 1) rd_launch((conv_pf_kernel<T, TAPS, NB, 1>), grid, dim3(256), lds, st, p, rdfin::current());
-            else rd_launch((conv_pf_kernel<T, TAPS, NB, 2>), grid, dim3(256), lds, st, p, rdfin::current());
-            return (int)hipGetLastError();
-        }
-    }
-    rd_launch((conv_kernel<T, TAPS, NB>), grid, dim3(256), lds, st, p, rdfin::current());
-    return (int)hipGetLastError();
+// conv_kernel<T, TAPS, NB> and, for bf16, its chunk-pipelined forms conv_pf_kernel<T, TAPS, NB, NQ>:
+// big_kernels[fp32][1x1][NB == 1][conv_kernel, NQ 1, NQ 2]
+#define RD_BIG_BF16(TAPS, NB) { RD_KERNEL(rd_thunk_conv, 72 * 1024, conv_kernel<bf16_t, TAPS, NB>), \
+                                RD_KERNEL(rd_thunk_conv, 72 * 1024, conv_pf_kernel<bf16_t, TAPS, NB, 1, 0, 0>), \
+                                RD_KERNEL(rd_thunk_conv, 72 * 1024, conv_pf_kernel<bf16_t, TAPS, NB, 2, 0, 0>) }   // two workgroups per CU; covers CinPad <= 1024
+#define RD_BIG_F32(TAPS, NB) { RD_KERNEL(rd_thunk_conv, 72 * 1024, conv_kernel<float, TAPS, NB>), {}, {} }
+rd_kernel_t big_kernels[2][2][2][3] = {{{RD_BIG_BF16(9, 2), RD_BIG_BF16(9, 1)}, {RD_BIG_BF16(1, 2), RD_BIG_BF16(1, 1)}},
+                                       {{RD_BIG_F32(9, 2), RD_BIG_F32(9, 1)}, {RD_BIG_F32(1, 2), RD_BIG_F32(1, 1)}}};
+#undef RD_BIG_BF16
+#undef RD_BIG_F32
+
+// which: 0 conv_kernel, 1 / 2 conv_pf_kernel<.., NQ>
+void big_route(const rd_conv_t& p, int dtype, bool nb2, int which, Route& r) {
+    rd_route_set(r, big_kernels[dtype != RD_BF16][p.taps != 9][!nb2][which], ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH),
+                 p.CoutPad / (nb2 ? 64 : 32), p.N, 256, conv_pf_lds(p, p.taps, nb2 ? 2 : 1));
 }
 
 }  // namespace
 
-static bool conv_big_nb2(const rd_conv_t& p, int dtype) {
+bool rd_conv_nb2(const rd_conv_t& p, int dtype) {
     bool nb2 = (p.CoutPad % 64) == 0;
     // small grids (the 25x25 / 50x50 levels): 32-channel tiles double the number of workgroups
     static const int nb1_below = rd_switch("RD_CONV_NB1_BELOW", 300);
@@ -158,22 +127,12 @@ static bool conv_big_nb2(const rd_conv_t& p, int dtype) {
     return nb2;
 }
 
-bool rd_conv_big_takes_ws(const rd_conv_t& p, int dtype) {
-    static const bool pp_off = rd_switch("RD_CONV_PP_OFF", 0) != 0;
-    return dtype == RD_BF16 && p.taps == 9 && conv_big_nb2(p, dtype) && !pp_off && rd_conv_ws_takes(p);
+bool rd_route_pf(const rd_conv_t& p, int dtype, bool nb2, Route& r) {
+    static const bool pf_off = rd_switch("RD_CONV_PF_OFF", 0) != 0;
+    const int nq = conv_pf_kind(p);
+    if (dtype != RD_BF16 || pf_off || !nq || conv_pf_lds(p, p.taps, nb2 ? 2 : 1) > (size_t)72 * 1024) return false;
+    big_route(p, dtype, nb2, nq, r);
+    return true;
 }
 
-bool rd_conv_big_stores_sources(const rd_conv_t& p, int dtype) {
-    return rd_conv_big_takes_ws(p, dtype) && rd_conv_ws_stores_sources(p);
-}
-
-int rd_conv_big_dispatch(const rd_conv_t& p, int dtype, hipStream_t st) {
-    const bool nb2 = conv_big_nb2(p, dtype);
-    if (dtype == RD_BF16) {
-        if (p.taps == 9) return nb2 ? launch_conv<bf16_t, 9, 2>(p, st) : launch_conv<bf16_t, 9, 1>(p, st);
-        return nb2 ? launch_conv<bf16_t, 1, 2>(p, st) : launch_conv<bf16_t, 1, 1>(p, st);
-    }
-    if (p.taps == 9) return nb2 ? launch_conv<float, 9, 2>(p, st) : launch_conv<float, 9, 1>(p, st);
-    return nb2 ? launch_conv<float, 1, 2>(p, st) : launch_conv<float, 1, 1>(p, st);
-}
-
+void rd_route_conv_kernel(const rd_conv_t& p, int dtype, bool nb2, Route& r) { big_route(p, dtype, nb2, 0, r); }

@@ -441,20 +441,23 @@ __global__ __launch_bounds__(512, 1) void conv_small_bwd_fused_kernel(const rd_c
 
 inline bool aligned16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
-template <int NSL, int NQ>
-int fused_launch_one(dim3 grid, hipStream_t st, const rd_conv_t& p, const FusedWg& fw, int tpw) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_bwd_fused_kernel<NSL, NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, FZ_LDS);
-        attr_set = true;
-    }
-    rd_launch((conv_small_bwd_fused_kernel<NSL, NQ>), grid, dim3(512), FZ_LDS, st, p, fw, tpw, rdfin::current());
-    return (int)hipGetLastError();
+// launched with (dgrad descriptor, wgrad descriptor): the kernel's FusedWg is the weight gradient's operands and partial-sum layout
+template <auto K> void fused_thunk(const Route& r, const void* dgrad, const void* wgrad, hipStream_t st) {
+    const rd_wgrad_t& w = *static_cast<const rd_wgrad_t*>(wgrad);
+    FusedWg fw;
+    fw.a[0] = w.a[0];
+    fw.a[1] = w.a[1];
+    fw.partial = w.partial;
+    fw.CoutPadW = (w.Cout + 15) / 16 * 16;
+    fw.CinPadW = (w.Cin + 15) / 16 * 16;
+    rd_launch(K, rd_route_grid(r), dim3(r.v.block), (size_t)r.v.lds, st, *static_cast<const rd_conv_t*>(dgrad), fw, r.v.iarg[0], rdfin::current());
 }
-int fused_launch(int nsl, int nq, dim3 grid, hipStream_t st, const rd_conv_t& p, const FusedWg& fw, int tpw) {
-    if (nq == 2) return nsl == 1 ? fused_launch_one<1, 2>(grid, st, p, fw, tpw) : nsl == 2 ? fused_launch_one<2, 2>(grid, st, p, fw, tpw) : fused_launch_one<4, 2>(grid, st, p, fw, tpw);
-    return nsl == 1 ? fused_launch_one<1, 1>(grid, st, p, fw, tpw) : nsl == 2 ? fused_launch_one<2, 1>(grid, st, p, fw, tpw) : fused_launch_one<4, 1>(grid, st, p, fw, tpw);
-}
+// conv_small_bwd_fused_kernel<NSL, NQ>: fused_kernels[NQ == 1][NSL 1 / 2 / 4]
+#define RD_FZ(...) RD_KERNEL(fused_thunk, FZ_LDS, __VA_ARGS__)
+rd_kernel_t fused_kernels[2][3] = {
+    {RD_FZ(conv_small_bwd_fused_kernel<1, 2>), RD_FZ(conv_small_bwd_fused_kernel<2, 2>), RD_FZ(conv_small_bwd_fused_kernel<4, 2>)},
+    {RD_FZ(conv_small_bwd_fused_kernel<1, 1>), RD_FZ(conv_small_bwd_fused_kernel<2, 1>), RD_FZ(conv_small_bwd_fused_kernel<4, 1>)}};
+#undef RD_FZ
 
 }  // namespace
 
@@ -491,51 +494,14 @@ bool rd_bwd_fused_ok(const rd_conv_t& p, const rd_wgrad_t& w, int dtype) {
     return true;
 }
 
-static int fused_tiles_per_wg(const rd_conv_t& p, int& gx) {
+// out[0]: the fused kernel, one 512-thread workgroup per CU, about one tile-time of pipeline fill + drain per workgroup; out[1]: the
+// workgroups' dW block sums -> dW (fixed order: deterministic) -- its own entry point so that the host can put it on the
+// weight-gradient lane, off the dgrad chain.  The workspace is one block of sums per workgroup: out[1]'s nsplit and pads.
+void rd_bwd_fused_route(const rd_conv_t& p, const rd_wgrad_t& w, Route out[2]) {
     const int ntiles = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH);
-    const bool limited = p.cu_limit > 0 && p.cu_limit < rd_num_cus();
-    const long slots = limited ? p.cu_limit : rd_num_cus();               // one 512-thread workgroup per CU
-    int tpw = 0;
-    double best = 1e30;
-    const int tmin = limited ? (int)(((long)ntiles * p.N + slots - 1) / slots) : 1;
-    for (int t = tmin < 1 ? 1 : tmin; (t <= 64 || limited) && t <= ntiles; ++t) {
-        const long wgs = (long)((ntiles + t - 1) / t) * p.N;
-        // whole rounds of resident workgroups; a workgroup pays about one tile-time of pipeline fill + drain
-        const double cost = (double)((wgs + slots - 1) / slots) * (t + 1.0);
-        if (cost < best - 1e-9) { best = cost; tpw = t; }
-        if (limited) break;
-    }
-    if (tpw <= 0) tpw = ntiles;
-    gx = (ntiles + tpw - 1) / tpw;
-    return tpw;
-}
-
-int64_t rd_bwd_fused_ws_bytes(const rd_conv_t& p, const rd_wgrad_t& w) {
-    int gx;
-    fused_tiles_per_wg(p, gx);
-    const int cop = (w.Cout + 15) / 16 * 16, cip = (w.Cin + 15) / 16 * 16;
-    return (int64_t)gx * p.N * 9 * cop * cip * (int64_t)sizeof(float);
-}
-
-int rd_bwd_fused_dispatch(const rd_conv_t& p, const rd_wgrad_t& w, hipStream_t st) {
-    int gx;
-    const int tpw = fused_tiles_per_wg(p, gx);
-    FusedWg fw;
-    fw.a[0] = w.a[0];
-    fw.a[1] = w.a[1];
-    fw.partial = w.partial;
-    fw.CoutPadW = (w.Cout + 15) / 16 * 16;
-    fw.CinPadW = (w.Cin + 15) / 16 * 16;
-    dim3 grid(gx, 1, p.N);
-    const int nl = (p.Cin + 7) / 8, nsl = nl <= 1 ? 1 : (nl <= 2 ? 2 : 4);
-    const int nq = p.src[0].mode == RD_SRC_BNBWD ? 2 : 1;
-    return fused_launch(nsl, nq, grid, st, p, fw, tpw);
-}
-
-// the workgroups' dW block sums -> dW (fixed order: deterministic); its own entry point so that the host can put it on the
-// weight-gradient lane, off the dgrad chain
-int rd_bwd_fused_reduce_dispatch(const rd_conv_t& p, const rd_wgrad_t& w, hipStream_t st) {
-    int gx;
-    fused_tiles_per_wg(p, gx);
-    return rd_wgrad_reduce_launch(w.partial, w.dW, gx * p.N, 9, w.Cout, w.Cin, (w.Cout + 15) / 16 * 16, (w.Cin + 15) / 16 * 16, w.beta, st);
+    const int tpw = rd_tiles_per_wg(p, ntiles, 1, 1.0, 64, 1), gx = (ntiles + tpw - 1) / tpw;
+    const int nl = (p.Cin + 7) / 8;
+    rd_route_set(out[0], fused_kernels[p.src[0].mode != RD_SRC_BNBWD][nl <= 1 ? 0 : (nl <= 2 ? 1 : 2)], gx, 1, p.N, 512, FZ_LDS);
+    out[0].v.iarg[0] = tpw;
+    rd_route_wgrad_reduce(w.partial, gx * p.N, 9, w.Cout, w.Cin, (w.Cout + 15) / 16 * 16, (w.Cin + 15) / 16 * 16, out[1]);
 }

@@ -20,26 +20,13 @@ __device__ int pf_trace_key;
 
 namespace {
 
-template <int TAPS, int NB, int TS>
-int launch_lean(const rd_conv_t& p, int ep, int nq, hipStream_t st) {
-    typedef bf16_t T;
-    const size_t lds = conv_pf_lds<TAPS, NB, TS>(p);
-    if (lds > (size_t)72 * 1024) return RD_CONV_PP_NA;
-    constexpr int THt = TileGeo<TS>::H, TWt = TileGeo<TS>::W;
-    dim3 grid(((p.W + TWt - 1) / TWt) * ((p.H + THt - 1) / THt), p.CoutPad / (NB * 32), p.N);
-    static bool attr = false;
-    if (!attr) {
-        const int lds_max = 72 * 1024;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pf_kernel<T, TAPS, NB, 1, 1, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pf_kernel<T, TAPS, NB, 1, 2, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pf_kernel<T, TAPS, NB, 2, 2, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        attr = true;
-    }
-    if (ep == 1) rd_launch((conv_pf_kernel<T, TAPS, NB, 1, 1, TS>), grid, dim3(256), lds, st, p, rdfin::current());
-    else if (nq == 1) rd_launch((conv_pf_kernel<T, TAPS, NB, 1, 2, TS>), grid, dim3(256), lds, st, p, rdfin::current());
-    else rd_launch((conv_pf_kernel<T, TAPS, NB, 2, 2, TS>), grid, dim3(256), lds, st, p, rdfin::current());
-    return (int)hipGetLastError();
-}
+// conv_pf_kernel<bf16_t, TAPS, NB, NQ, EP, TS>: lean_kernels[row][forward, gradient NQ 1, gradient NQ 2], rows as lean_row() counts them
+#define RD_LEAN_ROW(TAPS, NB, TS) { RD_KERNEL(rd_thunk_conv, 72 * 1024, conv_pf_kernel<bf16_t, TAPS, NB, 1, 1, TS>), \
+                                    RD_KERNEL(rd_thunk_conv, 72 * 1024, conv_pf_kernel<bf16_t, TAPS, NB, 1, 2, TS>), \
+                                    RD_KERNEL(rd_thunk_conv, 72 * 1024, conv_pf_kernel<bf16_t, TAPS, NB, 2, 2, TS>) }
+rd_kernel_t lean_kernels[6][3] = {RD_LEAN_ROW(9, 2, 1), RD_LEAN_ROW(9, 1, 1), RD_LEAN_ROW(9, 2, 0), RD_LEAN_ROW(9, 1, 0), RD_LEAN_ROW(1, 2, 0), RD_LEAN_ROW(1, 1, 0)};
+#undef RD_LEAN_ROW
+inline int lean_row(int taps, bool nb2, bool flat) { return (taps == 9 ? (flat ? 0 : 2) : 4) + (nb2 ? 0 : 1); }
 
 // 10 x 25 tiles where they put clearly more of the MFMA lanes on image pixels (sides 25 / 50 / 100 / 200: 0.61-0.89 -> 0.81-0.98).
 // conv_pf_kernel launches run in rounds of the resident workgroups (two per CU), so ALONE fewer tiles only help when they remove
@@ -62,16 +49,20 @@ inline bool flat_tiles(const rd_conv_t& p) {
 
 }  // namespace
 
-int rd_conv_pf_lean_dispatch(const rd_conv_t& p, bool nb2, hipStream_t st) {
+bool rd_route_pf_lean(const rd_conv_t& p, bool nb2, Route& r) {
+    static const bool lean_off = rd_switch("RD_CONV_PF_LEAN_OFF", 0) != 0;
+    if (lean_off || rd_switch("RD_CONV_PF_OFF", 0) != 0) return false;
     const int nq = conv_pf_kind(p);
-    if (!nq) return RD_CONV_PP_NA;
+    if (!nq) return false;
     const int ep = rd_conv_lean_mode(p, nb2 ? 64 : 32);
-    if (!ep || (ep == 1 && nq != 1)) return RD_CONV_PP_NA;
-    if (p.taps == 9) {
-        if (nb2 ? flat_tiles<2>(p) : flat_tiles<1>(p)) return nb2 ? launch_lean<9, 2, 1>(p, ep, nq, st) : launch_lean<9, 1, 1>(p, ep, nq, st);
-        return nb2 ? launch_lean<9, 2, 0>(p, ep, nq, st) : launch_lean<9, 1, 0>(p, ep, nq, st);
-    }
-    return nb2 ? launch_lean<1, 2, 0>(p, ep, nq, st) : launch_lean<1, 1, 0>(p, ep, nq, st);
+    if (!ep || (ep == 1 && nq != 1)) return false;
+    const bool flat = p.taps == 9 && (nb2 ? flat_tiles<2>(p) : flat_tiles<1>(p));
+    const size_t lds = conv_pf_lds(p, p.taps, nb2 ? 2 : 1, flat);
+    if (lds > (size_t)72 * 1024) return false;
+    const int th = flat ? TileGeo<1>::H : TH, tw = flat ? TileGeo<1>::W : TW;
+    rd_route_set(r, lean_kernels[lean_row(p.taps, nb2, flat)][ep == 1 ? 0 : nq], ((p.W + tw - 1) / tw) * ((p.H + th - 1) / th),
+                 p.CoutPad / (nb2 ? 64 : 32), p.N, 256, lds);
+    return true;
 }
 
 #ifdef RD_DEBUG_SWITCHES

@@ -230,14 +230,13 @@ __global__ __launch_bounds__(256, 2) void conv_pf_kernel(const rd_conv_t p, cons
 }
 
 
-// dynamic LDS of conv_pf_kernel: halo tile + weight chunk + BN coefficient rows + (register epilogues) bias / producer rows
-template <int TAPS, int NB, int TS = 0>
-inline size_t conv_pf_lds(const rd_conv_t& p) {
-    constexpr int HALO = (TAPS == 9) ? 1 : 0;
-    constexpr int TH = TileGeo<TS>::H, TW = TileGeo<TS>::W;
-    constexpr int PH = TH + 2 * HALO, PW = TileGeo<TS>::LdsPitch(HALO);
-    size_t lds = (size_t)(PH * PW * 4 + TAPS * NB * 32 * 4) * sizeof(uint4) + (size_t)3 * p.CinPad * sizeof(float) + (size_t)2 * NB * 32 * sizeof(float);
-    const size_t lds_epi = (size_t)TH * TW * 32 * sizeof(float) + 64 * sizeof(double);
+// dynamic LDS of conv_pf_kernel<T, taps, nb, NQ, EP, ts>: halo tile + weight chunk + BN coefficient rows + (register epilogues) bias / producer rows
+inline size_t conv_pf_lds(const rd_conv_t& p, int taps, int nb, int ts = 0) {
+    const int halo = (taps == 9) ? 1 : 0;
+    const int th = ts ? TileGeo<1>::H : TileGeo<0>::H, tw = ts ? TileGeo<1>::W : TileGeo<0>::W;
+    const int ph = th + 2 * halo, pw = ts ? TileGeo<1>::LdsPitch(halo) : TileGeo<0>::LdsPitch(halo);
+    size_t lds = (size_t)(ph * pw * 4 + taps * nb * 32 * 4) * sizeof(uint4) + (size_t)3 * p.CinPad * sizeof(float) + (size_t)2 * nb * 32 * sizeof(float);
+    const size_t lds_epi = (size_t)th * tw * 32 * sizeof(float) + 64 * sizeof(double);
     return lds < lds_epi ? lds_epi : lds;
 }
 

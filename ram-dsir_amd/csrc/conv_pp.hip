@@ -17,7 +17,7 @@
 // conv_pf_kernel runs the same work as fill -> barrier -> MFMA -> barrier with two workgroups per CU (fill VALU and MFMA
 // of one wave never overlap, LDS reads are waited for right before their MFMA, every tile starts with an exposed HBM
 // round trip).  Two kernels live here: conv_pp_kernel (4 waves, every wave does everything, LDS-staged epilogue) and
-// conv_ws_kernel (8 waves, MFMA waves + loader waves, register epilogues); rd_conv_pp_dispatch says which launch takes which.
+// conv_ws_kernel (8 waves, MFMA waves + loader waves, register epilogues); rd_route_ws / rd_route_pp (below) say which launch takes which.
 #include "conv_device.h"
 #include "conv_epilogue.h"
 #include "conv_dispatch.h"
@@ -813,7 +813,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(const rd_conv_t p, int 
 #pragma unroll
             for (int v = 0; v < 2; ++v) zq[mb][nb][v] = make_uint4(0, 0, 0, 0);
     // Where a lane's vectors of the destination tensors sit: 32-BIT byte offsets from the (wave-uniform) tensor base, one multiply of
-    // 24-bit operands each (rd_conv_ws_takes: the images of a destination number < 2^24 pixels and < 4 GB).  Written with size_t
+    // 24-bit operands each (rd_route_ws: the images of a destination number < 2^24 pixels and < 4 GB).  Written with size_t
     // indices, each of the sixteen addresses of a tile -- eight producer-tensor requests, eight gradient stores -- was ~35
     // instructions with two 64-bit multiply-adds and two quarter-rate 32-bit multiplies: ~2 000 cycles in front of the last K step's
     // MFMAs and ~2 000 more inside the epilogue of a 20 000-cycle tile (profiles/r06_ws_trace.txt, stamp "pref+g0").  The gradient
@@ -1005,7 +1005,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(const rd_conv_t p, int 
                             float da[S];
                             regroup(acc[mb][nb], v, da);
                             if (!pin[mb]) continue;
-                            // no load in this loop (destinations that accumulate go to conv_pf_kernel: rd_conv_pp_dispatch): with the old
+                            // no load in this loop (destinations that accumulate go to conv_pf_kernel: rd_route_ws): with the old
                             // gradient read here (`d.accumulate ? ld16(gp) : 0`), every vector waited vmcnt(0) -- i.e. for the previous
                             // vector's STORE to be acknowledged -- before its own arithmetic: eight serialized round trips per tile
                             // (6 500-11 000 cycles of epilogue against the forward mode's 2 000-3 000)
@@ -1080,13 +1080,52 @@ extern "C" int rd_debug_ws_trace(unsigned long long* out) {             // debug
 }
 #endif
 
-// does this launch run on conv_ws_kernel?  ONE definition for the dispatch below and for rd_conv_honours_src_out (conv_api.hip), which
-// tells the host whether a launch will write rd_src_t.out (only this kernel does)
-bool rd_conv_ws_takes(const rd_conv_t& p) {
+namespace {
+rd_kernel_t pp_kernel = RD_KERNEL(rd_thunk_conv_i, PP_LDS, conv_pp_kernel);
+// conv_ws_kernel<MODE, TS, BWD2, SOUT>; MODE 1 forward / 2 gradient, TS the tile shape, BWD2 the two-operand (BatchNorm-backward) loader, SOUT the
+// forms that also write rd_src_t.out.  ws_kernel() indexes it.
+#define RD_WS(TS, ...) RD_KERNEL(rd_thunk_conv_i, WsLds<TS>::LDS, __VA_ARGS__)
+rd_kernel_t ws_kernels[10] = {
+    RD_WS(0, conv_ws_kernel<1, 0, false, false>), RD_WS(0, conv_ws_kernel<2, 0, false, false>), RD_WS(1, conv_ws_kernel<1, 1, false, false>),
+    RD_WS(1, conv_ws_kernel<2, 1, false, false>), RD_WS(0, conv_ws_kernel<2, 0, true, false>), RD_WS(1, conv_ws_kernel<2, 1, true, false>),
+    RD_WS(0, conv_ws_kernel<1, 0, false, true>), RD_WS(1, conv_ws_kernel<1, 1, false, true>), RD_WS(0, conv_ws_kernel<2, 0, true, true>),
+    RD_WS(1, conv_ws_kernel<2, 1, true, true>)};
+#undef RD_WS
+inline rd_kernel_t& ws_kernel(int mode, bool flat, bool bwd2, bool sout) {
+    return ws_kernels[sout ? (mode == 1 ? 6 : 8) + flat : bwd2 ? 4 + flat : 2 * flat + (mode - 1)];
+}
+inline bool pp_class(const rd_conv_t& p, int skind) {         // what conv_pp.hip's kernels can run at all
+    static const bool pp_off = rd_switch("RD_CONV_PP_OFF", 0) != 0;
+    return !pp_off && p.taps == 9 && p.CoutPad % PP_NT == 0 && p.CinPad <= 32 * PP_MAX_CHUNKS && skind;
+}
+inline int pp_tiles(const rd_conv_t& p) { return ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.N * (p.CoutPad / PP_NT); }
+inline int pp_cus(const rd_conv_t& p) { return (p.cu_limit > 0 && p.cu_limit < rd_num_cus()) ? p.cu_limit : rd_num_cus(); }   // a side lane's budget (ramdsir.h)
+}  // namespace
+
+// conv_ws_kernel: launches that qualify for a register epilogue (conv_dispatch.h: 1 forward, 2 gradient into plain tensors) take the
+// warp-specialised kernel.  Layer timings (scripts/ab_layers.sh, us, previous kernel -> conv_ws_kernel):
+//   forward:   256->256 @50x50 102 -> 90, 128->128 @100x100 99 -> 85, 64->64 @200x200 96 -> 84, 128->64 @100x100 62 -> 54,
+//              64->64 @100x100 43 -> 38: every forward launch gains;
+//   gradient:  64->64 @200x200 153 -> 137, 128->128 @100x100 129 -> 122, but 128->128 @50x50 40 -> 52, 64->64 @100x100
+//              55 -> 62: with few tiles per CU the two-workgroup conv_pf_kernel streams the materialised dz better, so
+//              gradient launches need >= RD_CONV_WS_MIN2 tiles (round 2 default: 1536 = 6 per CU).
+//   Round 3, in the STEP (scripts/sweep_opts.sh, alternating): threshold 1536 5.06-5.07 ms, 800: 5.19, 400: 5.22, never: 5.01-5.02 --
+//   a gradient launch that takes whole CUs (512 threads, 154 KB LDS) keeps the weight-gradient lane's kernels off them for its
+//   whole duration; the two-workgroup conv_pf_kernel shares.  Default: never for gradients (the kernel mode stays, tests force it).
+//   Round 4: the gradient mode's MFMA waves had their eight producer-tensor loads and their eight stores each behind a vmcnt(0)
+//   (scripts/ws_trace.py: last K step 9 000-10 700 cycles, epilogue 6 500-11 000); with both fixed a tile takes ~15 000 cycles
+//   instead of ~24 000 and every >= 64-channel gradient launch is 15-20 % faster here than on conv_pf_kernel (dec.convu2.conv3
+//   103 -> 87 us, dec.convu3.conv3 85 -> 70, dec.convu4.conv3 84 -> 69, enc.convd3.* 40 -> 33).  In the step it needs a compute-unit
+//   budget (tuning.py dgrad_cus = 160: the persistent workgroups leave 96 CUs to the other lanes): 4.48 -> 4.43 ms
+//   (scripts/sweep_ws2.sh, alternating; 4.48 with the whole GPU, 4.51 with 128).  Default: every non-accumulating gradient launch.
+// It is the only kernel that WRITES the rd_src_t.out tensors it is given, and only its SOUT instantiations do: forward launches
+// (mode 1) and gradient launches on a BatchNorm-backward source (mode 2, two-operand loader).  A gradient launch on plain sources runs
+// conv_ws_kernel<2, TS>, which never stores what it stages.  Route.stores_sources says so to rd_conv_honours_src_out.
+bool rd_route_ws(const rd_conv_t& p, Route& r) {
     const int skind = pp_sources_kind(p);
-    if (p.taps != 9 || p.CoutPad % PP_NT || p.CinPad > 32 * PP_MAX_CHUNKS || !skind) return false;
+    if (!pp_class(p, skind)) return false;
     static const int ws = rd_switch("RD_CONV_WS", 3), ws_min2 = rd_switch("RD_CONV_WS_MIN2", 0);
-    const int tiles = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.N * (p.CoutPad / PP_NT);
+    const int tiles = pp_tiles(p);
     const int mode = rd_conv_lean_mode(p, PP_NT);
     const size_t tab = (size_t)(mode == 1 ? 1 : 2 * p.G) * p.CoutPad * sizeof(float);
     bool accumulates = false;                                  // gradient launches that add to an existing gradient stay with conv_pf_kernel
@@ -1102,104 +1141,40 @@ bool rd_conv_ws_takes(const rd_conv_t& p) {
     if (mode == 2)
         for (int i = 0; i < 2; ++i)
             if (p.dst[i].kind != RD_DST_NONE && !fits32((long long)p.N + p.dst[i].n_off, p.dst[i].Cd)) return false;
-    return mode && (ws & mode) && (mode == 1 || (tiles >= ws_min2 && !accumulates)) && tab <= (size_t)WsLds<0>::TAB_BYTES;
+    if (!(mode && (ws & mode) && (mode == 1 || (tiles >= ws_min2 && !accumulates)) && tab <= (size_t)WsLds<0>::TAB_BYTES)) return false;
+    // debug build only: RD_CONV_WS_EXP = timing experiments (-DRD_WS_EXP), RD_CONV_WS_TRACE_MIN = launches with at least
+    // that many tiles record the s_memtime trace (scripts/ws_trace.py); both ride in the high bits of the tile count
+    static const int ws_exp = rd_switch("RD_CONV_WS_EXP", 0), ws_trace_min = rd_switch("RD_CONV_WS_TRACE_MIN", 1 << 30);
+    // 10 x 25 tiles where they put more of the MFMA rows on image pixels (sides 50 / 100 / 200: fewer tiles per CU).  The twelve
+    // forward launches of the step that come here, alone (scripts/layer_bench.py, RD_CONV_WS_FLAT 0 -> 1): 574 -> 513 us summed
+    // (dec.convu4.conv3 81 -> 66, dec.convu3.conv3 78 -> 65, dec.convu2.conv3 84 -> 73, the 50-pixel levels 32-37 -> 29-33);
+    // step 4.97 -> 4.92 ms (scripts/sweep_opts.sh, three alternating pairs)
+    static const int ws_flat = rd_switch("RD_CONV_WS_FLAT", 1);
+    const int tiles1 = ((p.W + TileGeo<1>::W - 1) / TileGeo<1>::W) * ((p.H + TileGeo<1>::H - 1) / TileGeo<1>::H) * p.N * (p.CoutPad / PP_NT);
+    const bool flat = ws_flat && tiles1 * 1.04 < tiles;
+    const int nt = flat ? tiles1 : tiles, cus = pp_cus(p);
+    // RD_CONV_WS_TRACE_MODE (0 any / 1 forward / 2 gradient) and RD_CONV_WS_TRACE_CIN (0 any) narrow the traced launches inside a whole step
+    static const int ws_trace_mode = rd_switch("RD_CONV_WS_TRACE_MODE", 0), ws_trace_cin = rd_switch("RD_CONV_WS_TRACE_CIN", 0);
+    const bool traced = tiles >= ws_trace_min && (!ws_trace_mode || ws_trace_mode == mode) && (!ws_trace_cin || ws_trace_cin == p.Cin);
+    const bool stores = mode == 1 || skind == 2;
+    bool sout = false;                                         // a source asks for its staged values to be stored as well (ramdsir.h)
+    for (int i = 0; i < p.nsrc; ++i) sout = sout || p.src[i].out != nullptr;
+    rd_route_set(r, ws_kernel(mode, flat, skind == 2, sout && stores), nt < cus ? nt : cus, 1, 1, 512, flat ? WsLds<1>::LDS : WsLds<0>::LDS);
+    r.v.iarg[0] = nt | (ws_exp << 26) | (traced ? 1 << 25 : 0);
+    r.v.stores_sources = stores;
+    return true;
 }
 
-// does this launch also WRITE the rd_src_t.out tensors it is given?  Only the SOUT instantiations of conv_ws_kernel do: forward launches
-// (mode 1) and gradient launches on a BatchNorm-backward source (mode 2, two-operand loader).  A gradient launch on plain sources runs
-// conv_ws_kernel<2, TS>, which never stores what it stages.  ONE definition for the dispatch below and for rd_conv_honours_src_out.
-bool rd_conv_ws_stores_sources(const rd_conv_t& p) {
-    if (!rd_conv_ws_takes(p)) return false;
-    return rd_conv_lean_mode(p, PP_NT) == 1 || pp_sources_kind(p) == 2;
-}
-
-int rd_conv_pp_dispatch(const rd_conv_t& p, hipStream_t st) {
+// conv_pp_kernel (LDS-staged epilogue, any destination): measured (gpurun_out/lb_pp*.txt) 1.06-1.2x over conv_pf_kernel
+// with at most one tile per CU -- the 25x25 level -- and 0.7-0.9x on longer tile ranges, where its un-overlapped
+// epilogue (2100 VALU per tile and wave at one workgroup per CU) costs more than the pipelined K loop gains.
+bool rd_route_pp(const rd_conv_t& p, Route& r) {
     const int skind = pp_sources_kind(p);
-    if (p.taps != 9 || p.CoutPad % PP_NT || p.CinPad > 32 * PP_MAX_CHUNKS || !skind) return RD_CONV_PP_NA;
-    static int n_cu = 0;
-    if (!n_cu) {
-        n_cu = rd_num_cus();
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<0>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<0>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<1>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<1>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<2, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<0>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<2, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<1>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<1, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<0>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<1, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<1>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<2, 0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<0>::LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<2, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WsLds<1>::LDS);
-    }
-    const int tiles = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * p.N * (p.CoutPad / PP_NT);
-    const int cus = (p.cu_limit > 0 && p.cu_limit < n_cu) ? p.cu_limit : n_cu;     // a side lane's budget (ramdsir.h)
-    const int grid = tiles < cus ? tiles : cus;
-    // Launches that qualify for a register epilogue (conv_dispatch.h: 1 forward, 2 gradient into plain tensors) take the
-    // warp-specialised kernel.  Layer timings (scripts/ab_layers.sh, us, previous kernel -> conv_ws_kernel):
-    //   forward:   256->256 @50x50 102 -> 90, 128->128 @100x100 99 -> 85, 64->64 @200x200 96 -> 84, 128->64 @100x100 62 -> 54,
-    //              64->64 @100x100 43 -> 38: every forward launch gains;
-    //   gradient:  64->64 @200x200 153 -> 137, 128->128 @100x100 129 -> 122, but 128->128 @50x50 40 -> 52, 64->64 @100x100
-    //              55 -> 62: with few tiles per CU the two-workgroup conv_pf_kernel streams the materialised dz better, so
-    //              gradient launches need >= RD_CONV_WS_MIN2 tiles (round 2 default: 1536 = 6 per CU).
-    //   Round 3, in the STEP (scripts/sweep_opts.sh, alternating): threshold 1536 5.06-5.07 ms, 800: 5.19, 400: 5.22, never: 5.01-5.02 --
-    //   a gradient launch that takes whole CUs (512 threads, 154 KB LDS) keeps the weight-gradient lane's kernels off them for its
-    //   whole duration; the two-workgroup conv_pf_kernel shares.  Default: never for gradients (the kernel mode stays, tests force it).
-    //   Round 4: the gradient mode's MFMA waves had their eight producer-tensor loads and their eight stores each behind a vmcnt(0)
-    //   (scripts/ws_trace.py: last K step 9 000-10 700 cycles, epilogue 6 500-11 000); with both fixed a tile takes ~15 000 cycles
-    //   instead of ~24 000 and every >= 64-channel gradient launch is 15-20 % faster here than on conv_pf_kernel (dec.convu2.conv3
-    //   103 -> 87 us, dec.convu3.conv3 85 -> 70, dec.convu4.conv3 84 -> 69, enc.convd3.* 40 -> 33).  In the step it needs a compute-unit
-    //   budget (tuning.py dgrad_cus = 160: the persistent workgroups leave 96 CUs to the other lanes): 4.48 -> 4.43 ms
-    //   (scripts/sweep_ws2.sh, alternating; 4.48 with the whole GPU, 4.51 with 128).  Default: every non-accumulating gradient launch.
-    static const int ws = rd_switch("RD_CONV_WS", 3), ws_min2 = rd_switch("RD_CONV_WS_MIN2", 0);
-    const int mode = rd_conv_lean_mode(p, PP_NT);
-    const size_t tab = (size_t)(mode == 1 ? 1 : 2 * p.G) * p.CoutPad * sizeof(float);
-    bool accumulates = false;                                  // gradient launches that add to an existing gradient stay with conv_pf_kernel
-    if (mode == 2)
-        for (int i = 0; i < 2; ++i) accumulates = accumulates || (p.dst[i].kind != RD_DST_NONE && p.dst[i].accumulate);
-    const bool takes = rd_conv_ws_takes(p);
-    if (skind == 2 && !takes) return RD_CONV_PP_NA;            // a two-operand source runs on conv_ws_kernel<2, *, true> or not here at all
-    if (takes) {
-        // debug build only: RD_CONV_WS_EXP = timing experiments (-DRD_WS_EXP), RD_CONV_WS_TRACE_MIN = launches with at least
-        // that many tiles record the s_memtime trace (scripts/ws_trace.py); both ride in the high bits of the tile count
-        static const int ws_exp = rd_switch("RD_CONV_WS_EXP", 0), ws_trace_min = rd_switch("RD_CONV_WS_TRACE_MIN", 1 << 30);
-        // 10 x 25 tiles where they put more of the MFMA rows on image pixels (sides 50 / 100 / 200: fewer tiles per CU).  The twelve
-        // forward launches of the step that come here, alone (scripts/layer_bench.py, RD_CONV_WS_FLAT 0 -> 1): 574 -> 513 us summed
-        // (dec.convu4.conv3 81 -> 66, dec.convu3.conv3 78 -> 65, dec.convu2.conv3 84 -> 73, the 50-pixel levels 32-37 -> 29-33);
-        // step 4.97 -> 4.92 ms (scripts/sweep_opts.sh, three alternating pairs)
-        static const int ws_flat = rd_switch("RD_CONV_WS_FLAT", 1);
-        const int tiles1 = ((p.W + TileGeo<1>::W - 1) / TileGeo<1>::W) * ((p.H + TileGeo<1>::H - 1) / TileGeo<1>::H) * p.N * (p.CoutPad / PP_NT);
-        const bool flat = ws_flat && tiles1 * 1.04 < tiles;
-        const int nt = flat ? tiles1 : tiles, grid_ws = nt < cus ? nt : cus;
-        // RD_CONV_WS_TRACE_MODE (0 any / 1 forward / 2 gradient) and RD_CONV_WS_TRACE_CIN (0 any) narrow the traced launches inside a whole step
-        static const int ws_trace_mode = rd_switch("RD_CONV_WS_TRACE_MODE", 0), ws_trace_cin = rd_switch("RD_CONV_WS_TRACE_CIN", 0);
-        const bool traced = tiles >= ws_trace_min && (!ws_trace_mode || ws_trace_mode == mode) && (!ws_trace_cin || ws_trace_cin == p.Cin);
-        const int arg = nt | (ws_exp << 26) | (traced ? 1 << 25 : 0);
-        bool sout = false;                                     // a source asks for its staged values to be stored as well (ramdsir.h)
-        for (int i = 0; i < p.nsrc; ++i) sout = sout || p.src[i].out != nullptr;
-        sout = sout && rd_conv_ws_stores_sources(p);
-        if (mode == 1 && sout) {
-            if (flat) rd_launch((conv_ws_kernel<1, 1, false, true>), dim3(grid_ws), dim3(512), WsLds<1>::LDS, st, p, arg, rdfin::current());
-            else rd_launch((conv_ws_kernel<1, 0, false, true>), dim3(grid_ws), dim3(512), WsLds<0>::LDS, st, p, arg, rdfin::current());
-        } else if (mode == 1) {
-            if (flat) rd_launch((conv_ws_kernel<1, 1>), dim3(grid_ws), dim3(512), WsLds<1>::LDS, st, p, arg, rdfin::current());
-            else rd_launch((conv_ws_kernel<1, 0>), dim3(grid_ws), dim3(512), WsLds<0>::LDS, st, p, arg, rdfin::current());
-        } else if (skind == 2 && sout) {
-            if (flat) rd_launch((conv_ws_kernel<2, 1, true, true>), dim3(grid_ws), dim3(512), WsLds<1>::LDS, st, p, arg, rdfin::current());
-            else rd_launch((conv_ws_kernel<2, 0, true, true>), dim3(grid_ws), dim3(512), WsLds<0>::LDS, st, p, arg, rdfin::current());
-        } else if (skind == 2) {
-            if (flat) rd_launch((conv_ws_kernel<2, 1, true>), dim3(grid_ws), dim3(512), WsLds<1>::LDS, st, p, arg, rdfin::current());
-            else rd_launch((conv_ws_kernel<2, 0, true>), dim3(grid_ws), dim3(512), WsLds<0>::LDS, st, p, arg, rdfin::current());
-        } else {
-            if (flat) rd_launch((conv_ws_kernel<2, 1>), dim3(grid_ws), dim3(512), WsLds<1>::LDS, st, p, arg, rdfin::current());
-            else rd_launch((conv_ws_kernel<2, 0>), dim3(grid_ws), dim3(512), WsLds<0>::LDS, st, p, arg, rdfin::current());
-        }
-        return (int)hipGetLastError();
-    }
-    // conv_pp_kernel (LDS-staged epilogue, any destination): measured (gpurun_out/lb_pp*.txt) 1.06-1.2x over conv_pf_kernel
-    // with at most one tile per CU -- the 25x25 level -- and 0.7-0.9x on longer tile ranges, where its un-overlapped
-    // epilogue (2100 VALU per tile and wave at one workgroup per CU) costs more than the pipelined K loop gains.
+    if (!pp_class(p, skind) || skind == 2) return false;      // a two-operand source runs on conv_ws_kernel<2, *, true> or not here at all
     static const bool pp_all = rd_switch("RD_CONV_PP_ALL", 0) != 0;
-    if (tiles > n_cu && !pp_all) return RD_CONV_PP_NA;
-    rd_launch(conv_pp_kernel, dim3(grid), dim3(256), PP_LDS, st, p, tiles, rdfin::current());
-    return (int)hipGetLastError();
+    const int tiles = pp_tiles(p), cus = pp_cus(p);
+    if (tiles > rd_num_cus() && !pp_all) return false;
+    rd_route_set(r, pp_kernel, tiles < cus ? tiles : cus, 1, 1, 256, PP_LDS);
+    r.v.iarg[0] = tiles;
+    return true;
 }

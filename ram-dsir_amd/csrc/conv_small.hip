@@ -484,64 +484,33 @@ __global__ __launch_bounds__(256, 2) void conv_small_stage_kernel(const rd_conv_
     }
 }
 
-template <typename T, int TAPS, bool SRCG, int EPI>
-int launch_conv_small(const rd_conv_t& p, hipStream_t st) {
-    constexpr int HALO = (TAPS == 9) ? 1 : 0;
-    constexpr int PH = TH + 2 * HALO, PW = TW + 2 * HALO;
-    constexpr bool REG_EPI = !SRCG && EPI <= 1;            // register epilogue where it stays spill-free
-    const size_t lds = (size_t)(PH * PW * 4 + TAPS * 32 * 4) * sizeof(uint4) +
-                       (REG_EPI ? (size_t)64 * sizeof(double) + 64 * sizeof(float) + rdfin::FIN_LDS_FLOATS * sizeof(float)
-                                : (size_t)TH * TW * 32 * sizeof(float) + 64 * sizeof(double));
-    const int ntiles = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH);
-    static int tpw_env = -1;
-    if (tpw_env < 0) tpw_env = rd_switch("RD_TPW", 0);
-    // tiles per workgroup: the launch runs in rounds of `slots` resident workgroups (2 per CU); pick the
-    // count whose last round is (nearly) full -- e.g. 16 images x 650 tiles: 4 tiles/workgroup is 6 rounds
-    // x 4 tile-times, 21 tiles/workgroup is 1 round x 21 -- charging half a tile-time per workgroup prologue
-    int tpw = tpw_env;
-    if (tpw <= 0) {
-        const bool limited = p.cu_limit > 0 && p.cu_limit < rd_num_cus();
-        const long slots = 2L * (limited ? p.cu_limit : rd_num_cus());
-        double best = 1e30;
-        // a limited launch (side lane: ramdsir.h cu_limit) must fit ONE round of its budget, however many tiles that takes
-        const int tmin = limited ? (int)(((long)ntiles * p.N + slots - 1) / slots) : 1;
-        for (int t = tmin < 1 ? 1 : tmin; (t <= 32 || limited) && t <= ntiles; ++t) {
-            const long wgs = (long)((ntiles + t - 1) / t) * p.N;
-            const double cost = (double)((wgs + slots - 1) / slots) * (t + 0.5);
-            if (cost < best - 1e-9) { best = cost; tpw = t; }
-            if (limited) break;                             // the smallest count that fits is the one
-        }
-        if (tpw <= 0) tpw = ntiles;
-    }
-    dim3 grid((ntiles + tpw - 1) / tpw, 1, p.N);
-    static bool attr_set = false;
-    if constexpr (REG_EPI) {
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_kernel<T, TAPS, SRCG, EPI>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set = true;
-        }
-        rd_launch((conv_small_kernel<T, TAPS, SRCG, EPI>), grid, dim3(256), lds, st, p, tpw, rdfin::current());
-    } else {
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_stage_kernel<T, TAPS, SRCG, EPI>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set = true;
-        }
-        rd_launch((conv_small_stage_kernel<T, TAPS, SRCG, EPI>), grid, dim3(256), lds, st, p, tpw, rdfin::current());
-    }
-    return (int)hipGetLastError();
+// Per (T, TAPS): sources made of whole channel slots (SRCG false) with epilogue 0 forward / 1 plain gradient on conv_small_kernel (register
+// epilogue, where it stays spill-free), the pooling / upsampling / narrow gradients (3, 4, 2) and every SRCG launch on conv_small_stage_kernel.
+// small_kernels[fp32][1x1][column], columns as small_col() counts them
+#define RD_SMALL(...) RD_KERNEL(rd_thunk_conv_i, RD_ATTR_LDS, __VA_ARGS__)
+#define RD_SMALL_ROW(T, TAPS) { RD_SMALL(conv_small_kernel<T, TAPS, false, 0>), RD_SMALL(conv_small_kernel<T, TAPS, false, 1>), \
+                             RD_SMALL(conv_small_stage_kernel<T, TAPS, false, 3>), RD_SMALL(conv_small_stage_kernel<T, TAPS, false, 4>), \
+                             RD_SMALL(conv_small_stage_kernel<T, TAPS, false, 2>), RD_SMALL(conv_small_stage_kernel<T, TAPS, true, 0>), \
+                             RD_SMALL(conv_small_stage_kernel<T, TAPS, true, 1>), RD_SMALL(conv_small_stage_kernel<T, TAPS, true, 2>) }
+rd_kernel_t small_kernels[2][2][8] = {{RD_SMALL_ROW(bf16_t, 9), RD_SMALL_ROW(bf16_t, 1)}, {RD_SMALL_ROW(float, 9), RD_SMALL_ROW(float, 1)}};
+#undef RD_SMALL_ROW
+#undef RD_SMALL
+inline int small_col(bool srcg, int epi) {
+    if (srcg) return 5 + (epi > 2 ? 2 : epi);               // the staged epilogue 2 handles every gradient destination
+    return epi == 0 ? 0 : epi == 1 ? 1 : epi == 3 ? 2 : epi == 4 ? 3 : 4;
 }
 
-template <typename T, int TAPS>
-int dispatch_conv_small(const rd_conv_t& p, hipStream_t st) {
-    constexpr int S = Slot<T>::N;
+}  // namespace
+
+void rd_route_small(const rd_conv_t& p, int dtype, Route& r) {
+    const int S = dtype == RD_BF16 ? 8 : 4, HALO = (p.taps == 9) ? 1 : 0;
+    const int PH = TH + 2 * HALO, PW = TW + 2 * HALO;
     bool srcg = false;
     for (int i = 0; i < p.nsrc; ++i) {
         const int m = p.src[i].mode;
         if (!(m == RD_SRC_RAW || m == RD_SRC_AFF || m == RD_SRC_AFFACT || m == RD_SRC_BNBWD) || (p.src[i].C % S)) srcg = true;
     }
-    int epi = 0;
+    int epi = 0;                                            // forward: store_vec handles narrow outputs
     if (p.emode == 1) {
         epi = 1;
         bool pool = false, upy = false, narrow = false;
@@ -556,31 +525,14 @@ int dispatch_conv_small(const rd_conv_t& p, hipStream_t st) {
         else if (upy) epi = 3;
         else if (pool) epi = 4;
         else if (narrow) epi = 2;
-    } else if (p.Cout % S) {
-        epi = 0;                                           // store_vec handles narrow outputs
     }
-#define RD_CS(SG, EP) return launch_conv_small<T, TAPS, SG, EP>(p, st)
-    if (!srcg) {
-        if (epi == 0) RD_CS(false, 0);
-        if (epi == 1) RD_CS(false, 1);
-        if (epi == 3) RD_CS(false, 3);
-        if (epi == 4) RD_CS(false, 4);
-        RD_CS(false, 2);
-    }
-    if (epi == 0) RD_CS(true, 0);
-    if (epi == 1) RD_CS(true, 1);
-    RD_CS(true, 2);
-#undef RD_CS
+    const bool reg_epi = !srcg && epi <= 1;
+    const size_t lds = (size_t)(PH * PW * 4 + p.taps * 32 * 4) * sizeof(uint4) +
+                       (reg_epi ? (size_t)64 * sizeof(double) + 64 * sizeof(float) + rdfin::FIN_LDS_FLOATS * sizeof(float)
+                                : (size_t)TH * TW * 32 * sizeof(float) + 64 * sizeof(double));
+    const int ntiles = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH);
+    static const int tpw_env = rd_switch("RD_TPW", 0);
+    const int tpw = tpw_env > 0 ? tpw_env : rd_tiles_per_wg(p, ntiles, 2, 0.5, 32, 1);      // two workgroups per CU, half a tile-time of prologue
+    rd_route_set(r, small_kernels[dtype != RD_BF16][p.taps != 9][small_col(srcg, epi)], (ntiles + tpw - 1) / tpw, 1, p.N, 256, lds);
+    r.v.iarg[0] = tpw;
 }
-
-}  // namespace
-
-int rd_conv_small_dispatch(const rd_conv_t& p, int dtype, hipStream_t st) {
-    if (dtype == RD_BF16 && p.taps == 9 && p.emode == 0) {                // forward launches: conv_small_fwd_kernel where it applies
-        const int r = rd_conv_small_fwd_dispatch(p, dtype, st);
-        if (r != RD_CONV_PP_NA) return r;
-    }
-    if (dtype == RD_BF16) return p.taps == 9 ? dispatch_conv_small<bf16_t, 9>(p, st) : dispatch_conv_small<bf16_t, 1>(p, st);
-    return p.taps == 9 ? dispatch_conv_small<float, 9>(p, st) : dispatch_conv_small<float, 1>(p, st);
-}
-

@@ -469,92 +469,69 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv_small_fwd_kernel(const
 
 inline bool sw_aligned16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
+template <auto K> void sw_thunk(const Route& r, const void* p, const void* b, hipStream_t st) {
+#ifdef RD_DEBUG_SWITCHES
+    static bool jit_set = false;                             // debug library, RD_SW_JITTER: the kernels' flag, set before the first launch
+    if (!jit_set) {
+        const int j = rd_switch("RD_SW_JITTER", 0);
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(sw_jitter_flag), &j, sizeof(int));
+        jit_set = true;
+    }
+#endif
+    rd_thunk_conv_i<K>(r, p, b, st);
+}
+
+// conv_small_fwd_kernel<NSL, OUTV, XP, NWV>: NSL input channel slots (1 / 2 / 4), OUTV the output form (2: 32 channels, 1: 16, 3: <= 4,
+// 0: any), NWV waves per workgroup.  sw_kernels[NSL 1 / 2 / 4][OUTV 2 / 1 / 3 / 0][NWV 8 / 4]
+#define RD_SW(...) RD_KERNEL(sw_thunk, SW_LDS, __VA_ARGS__)
+#define RD_SW_PAIR(NSL, OUTV, XP) { RD_SW(conv_small_fwd_kernel<NSL, OUTV, XP, 8>), RD_SW(conv_small_fwd_kernel<NSL, OUTV, XP, 4>) }
+#define RD_SW_ROW(NSL) { RD_SW_PAIR(NSL, 2, 0), RD_SW_PAIR(NSL, 1, 0), RD_SW_PAIR(NSL, 3, 0), RD_SW_PAIR(NSL, 0, 0) }
+#ifdef RD_DEBUG_SWITCHES
+// timing experiments on the 32 -> 32 kernel (RD_SW_EXP = XP)
+const int sw_exp_xp[12] = {1, 2, 3, 4, 5, 6, 18, 22, 7, 19, 23, 32};
+rd_kernel_t sw_exp_kernels[12][2] = {RD_SW_PAIR(4, 2, 1), RD_SW_PAIR(4, 2, 2), RD_SW_PAIR(4, 2, 3), RD_SW_PAIR(4, 2, 4), RD_SW_PAIR(4, 2, 5), RD_SW_PAIR(4, 2, 6),
+                                     RD_SW_PAIR(4, 2, 18), RD_SW_PAIR(4, 2, 22), RD_SW_PAIR(4, 2, 7), RD_SW_PAIR(4, 2, 19), RD_SW_PAIR(4, 2, 23), RD_SW_PAIR(4, 2, 32)};
+#endif
+rd_kernel_t sw_kernels[3][4][2] = {RD_SW_ROW(1), RD_SW_ROW(2), RD_SW_ROW(4)};
+#undef RD_SW_ROW
+#undef RD_SW_PAIR
+#undef RD_SW
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-// forward launches of conv_small's class with whole 16-byte channel slots and single-operand sources; RD_CONV_PP_NA otherwise
-int rd_conv_small_fwd_dispatch(const rd_conv_t& p, int dtype, hipStream_t st) {
+// forward launches of conv_small's class with whole 16-byte channel slots and single-operand sources
+bool rd_route_small_fwd(const rd_conv_t& p, int dtype, Route& r) {
     static const int on = rd_switch("RD_CONV_SMALL_FWD", 1);
-    if (!on || dtype != RD_BF16 || p.taps != 9 || p.emode != 0 || p.CinPad != 32 || p.CoutPad != 32 || p.Cout > 32) return RD_CONV_PP_NA;
+    if (!on || dtype != RD_BF16 || p.taps != 9 || p.emode != 0 || p.CinPad != 32 || p.CoutPad != 32 || p.Cout > 32) return false;
     for (int i = 0; i < p.nsrc; ++i) {
         const rd_src_t& s = p.src[i];
-        if (!(s.mode == RD_SRC_RAW || s.mode == RD_SRC_AFF || s.mode == RD_SRC_AFFACT) || s.C % 8 || !sw_aligned16(s.ptr)) return RD_CONV_PP_NA;
+        if (!(s.mode == RD_SRC_RAW || s.mode == RD_SRC_AFF || s.mode == RD_SRC_AFFACT) || s.C % 8 || !sw_aligned16(s.ptr)) return false;
     }
-    if (!sw_aligned16(p.w) || ((p.Cout % 8) == 0 && !sw_aligned16(p.out))) return RD_CONV_PP_NA;
-    if ((size_t)p.N * p.H * p.W * 32 >= (1ull << 31)) return RD_CONV_PP_NA;        // 32-bit element offsets inside the kernel
+    if (!sw_aligned16(p.w) || ((p.Cout % 8) == 0 && !sw_aligned16(p.out))) return false;
+    if ((size_t)p.N * p.H * p.W * 32 >= (1ull << 31)) return false;        // 32-bit element offsets inside the kernel
     const int ntiles = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH);
-    const bool limited = p.cu_limit > 0 && p.cu_limit < rd_num_cus();
-    const int nl_ = (p.Cin + 7) / 8;
+    const int nl = (p.Cin + 7) / 8;
     static const int nwv_sw = rd_switch("RD_SW_NWV", RD_SW_NWV_DEFAULT);             // 8: one 512-thread workgroup per CU; 4: two of 256
     // two rows per wave need a second row accumulator, twice the fragment offsets and loader items: the 32-channel-input instantiations
     // (72 registers of weights) spill 200-470 bytes per lane that way and stay on one workgroup per CU
     static const int nwv_mask = rd_switch("RD_SW_NWV_MASK", 15);              // debug: 1 Cout 16, 2 Cout 32, 4 Cout <= 4 / other, 8 inputs of <= 8 channels
-    const int cls = (nl_ <= 1 ? 8 : (p.Cout == 16 ? 1 : (p.Cout == 32 ? 2 : 4)));
-    const int nwv = (nwv_sw == 4 && nl_ <= 2 && (nwv_mask & cls)) ? 4 : 8;
-    const long slots = (long)(limited ? p.cu_limit : rd_num_cus()) * (8 / nwv);
-    // tiles per workgroup: whole rounds of resident workgroups; a workgroup pays about two tile-times of pipeline fill + drain
-    int tpw = 0;
-    double best = 1e30;
-    const int tmin = limited ? (int)(((long)ntiles * p.N + slots - 1) / slots) : 1;
-    for (int t = tmin < 1 ? 1 : tmin; (t <= 64 || limited) && t <= ntiles; ++t) {
-        const long wgs = (long)((ntiles + t - 1) / t) * p.N;
-        const double cost = (double)((wgs + slots - 1) / slots) * (t + 2.0);
-        if (cost < best - 1e-9) { best = cost; tpw = t; }
-        if (limited) break;
-    }
-    if (tpw <= 0) tpw = ntiles;
-    tpw = (tpw + SW_NSET - 1) / SW_NSET * SW_NSET;          // the tile loop is unrolled by the register sets: whole groups, fewer ghost tiles
+    const int cls = (nl <= 1 ? 8 : (p.Cout == 16 ? 1 : (p.Cout == 32 ? 2 : 4)));
+    const int nwv = (nwv_sw == 4 && nl <= 2 && (nwv_mask & cls)) ? 4 : 8;
+    // tiles per workgroup: a workgroup pays about two tile-times of pipeline fill + drain; the tile loop is unrolled by the register
+    // sets: whole groups, fewer ghost tiles
+    int tpw = rd_tiles_per_wg(p, ntiles, 8 / nwv, 2.0, 64, SW_NSET);
     static const int tpw_forced = rd_switch("RD_SW_TPW", 0);          // debug build: the tests force multi-tile workgroups on small images
     if (tpw_forced > 0) tpw = tpw_forced < ntiles ? tpw_forced : ntiles;
-    dim3 grid((ntiles + tpw - 1) / tpw, 1, p.N);
-    const int nl = (p.Cin + 7) / 8;
-#define RD_SW_LAUNCH(NSL, OUTV, XP) do { \
-        static bool attr_set = false; \
-        if (!attr_set) { \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_fwd_kernel<NSL, OUTV, XP, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS); \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_fwd_kernel<NSL, OUTV, XP, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS); \
-            attr_set = true; \
-        } \
-        if (nwv == 4) rd_launch((conv_small_fwd_kernel<NSL, OUTV, XP, 4>), grid, dim3(256), SW_LDS, st, p, tpw, rdfin::current()); \
-        else rd_launch((conv_small_fwd_kernel<NSL, OUTV, XP, 8>), grid, dim3(512), SW_LDS, st, p, tpw, rdfin::current()); \
-        return (int)hipGetLastError(); \
-    } while (0)
-#ifdef RD_DEBUG_SWITCHES
-    if (nl > 2 && p.Cout == 32) {                           // timing experiments on the 32 -> 32 kernel
-        switch (rd_switch("RD_SW_EXP", 0)) {
-        case 1: RD_SW_LAUNCH(4, 2, 1);
-        case 2: RD_SW_LAUNCH(4, 2, 2);
-        case 3: RD_SW_LAUNCH(4, 2, 3);
-        case 4: RD_SW_LAUNCH(4, 2, 4);
-        case 5: RD_SW_LAUNCH(4, 2, 5);
-        case 6: RD_SW_LAUNCH(4, 2, 6);
-        case 18: RD_SW_LAUNCH(4, 2, 18);
-        case 22: RD_SW_LAUNCH(4, 2, 22);
-        case 7: RD_SW_LAUNCH(4, 2, 7);
-        case 19: RD_SW_LAUNCH(4, 2, 19);
-        case 23: RD_SW_LAUNCH(4, 2, 23);
-        case 32: RD_SW_LAUNCH(4, 2, 32);
-        default: break;
-        }
-    }
-#endif
-#ifdef RD_DEBUG_SWITCHES
-    {
-        static bool jit_set = false;
-        if (!jit_set) {
-            const int j = rd_switch("RD_SW_JITTER", 0);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(sw_jitter_flag), &j, sizeof(int));
-            jit_set = true;
-        }
-    }
-#endif
     static const int narrow_on = rd_switch("RD_SW_NARROW", 1);
-    const int outv = p.Cout == 32 ? 2 : (p.Cout == 16 ? 1 : ((p.Cout <= 4 && narrow_on) ? 3 : 0));
-#define RD_SW_OUT(NSL) do { if (outv == 2) RD_SW_LAUNCH(NSL, 2, 0); if (outv == 1) RD_SW_LAUNCH(NSL, 1, 0); \
-                            if (outv == 3) RD_SW_LAUNCH(NSL, 3, 0); RD_SW_LAUNCH(NSL, 0, 0); } while (0)
-    if (nl <= 1) RD_SW_OUT(1);
-    if (nl <= 2) RD_SW_OUT(2);
-    RD_SW_OUT(4);
-#undef RD_SW_OUT
-#undef RD_SW_LAUNCH
+    const int outv = p.Cout == 32 ? 0 : (p.Cout == 16 ? 1 : ((p.Cout <= 4 && narrow_on) ? 2 : 3));      // column of sw_kernels
+    rd_kernel_t* k = &sw_kernels[nl <= 1 ? 0 : (nl <= 2 ? 1 : 2)][outv][nwv == 4];
+#ifdef RD_DEBUG_SWITCHES
+    if (nl > 2 && p.Cout == 32)
+        for (int i = 0; i < 12; ++i)
+            if (sw_exp_xp[i] == rd_switch("RD_SW_EXP", 0)) k = &sw_exp_kernels[i][nwv == 4];
+#endif
+    rd_route_set(r, *k, (ntiles + tpw - 1) / tpw, 1, p.N, 64 * nwv, SW_LDS);
+    r.v.iarg[0] = tpw;
+    return true;
 }

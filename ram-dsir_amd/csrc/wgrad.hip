@@ -951,218 +951,142 @@ bool wgrad_slots_ok(const rd_wgrad_t& p) {
     return p.dz.C % 8 == 0;
 }
 
-struct WgradGeom {
-    int MB, NB, KS, CoutPadW, CinPadW, gx, total_tiles, nsplit;
-    bool c16;
-    bool sym;              // wgrad_sym_kernel: 128 gradient channels x 64 input channels per workgroup
-};
-
-template <typename T>
-WgradGeom wgrad_geom(const rd_wgrad_t& p) {
-    WgradGeom g;
-    g.c16 = false;
-    g.sym = false;
-    // 16 x 16 blocks (v_mfma_f32_16x16x32_bf16, 3 workgroups/CU): the 16-channel layers, and -- a grid of such blocks,
-    // transpose-read kernel only -- the layers with <= 16 output channels on 32 input channels (dec.out1 32->2,
-    // dec.convu1.conv2 32->16, rec.convu1.conv1 32->16), which would leave half of every 32 x 32 block's rows empty
-    if (sizeof(T) == 2 && p.Cout <= 16 && p.Cin <= (rd_switch("RD_WG_C16_GRID", 1) ? 32 : 16) && wgrad_pf_ok(p) && rd_switch("RD_WG_TR_OFF", 0) == 0) {
-        g.c16 = true;
-        g.MB = g.NB = 1;                                   // blocks per WORKGROUP
-        g.KS = 4;
-        g.CoutPadW = 16;
-        g.CinPadW = (p.Cin + 15) / 16 * 16;
-        g.total_tiles = p.N * ((p.H + TH - 1) / TH) * ((p.W + TW - 1) / TW);
-        // exactly the resident set (no second, partially filled round) at 3 workgroups/CU
-        // (cu_limit does not apply: these layers are the 400x400 / 200x200 ones, HBM-bound, and want every CU's load path)
-        int gx = 3 * rd_num_cus() / (g.CinPadW / 16);
-        if (gx > g.total_tiles) gx = g.total_tiles;
-        g.gx = gx < 1 ? 1 : gx;
-        g.nsplit = g.gx;
-        return g;
-    }
-    const int cout32 = (p.Cout + 31) / 32, cin32 = (p.Cin + 31) / 32;
-    // fp32 keeps 32x32 blocks (LDS budget); bf16 uses 64-wide tiles where the layer has them
-    g.MB = (sizeof(T) == 2 && cout32 % 2 == 0 && rd_switch("RD_WG_MB_MAX", 2) >= 2) ? 2 : 1;
-    g.NB = (sizeof(T) == 2 && cin32 % 2 == 0 && rd_switch("RD_WG_NB_MAX", 2) >= 2) ? 2 : 1;
-    g.KS = 4 / (g.MB * g.NB);
-    g.CoutPadW = cout32 * 32;
-    g.CinPadW = cin32 * 32;
-    g.total_tiles = p.N * ((p.H + TH - 1) / TH) * ((p.W + TW - 1) / TW);
-    int pairs = (g.CoutPadW / (g.MB * 32)) * (g.CinPadW / (g.NB * 32));
-    // 3x3 layers with whole 128-channel blocks of gradient channels on plain sources: the symmetric eight-wave kernel, half as many
-    // workgroups per pixel split (each owns 128 x 64 channels), so twice the splits on the same compute-unit budget
-    if (sizeof(T) == 2 && p.taps == 9 && g.MB == 2 && g.NB == 2 && g.CoutPadW % 128 == 0 && wgrad_pf_ok(p) && p.G * (2 * 64 + 3 * 128) * 4 <= 16384 && (p.na == 1 || p.a[0].C % 64 == 0) &&
-        rd_switch("RD_WG_WS", 1) && rd_switch("RD_WG_SYM", RD_WG_SYM_DEFAULT) && rd_switch("RD_WG_TR_OFF", 0) == 0) {
-        g.sym = true;
-        pairs /= 2;
-    }
-    // these kernels hold 144 accumulator registers per lane -> one workgroup per CU is resident: launching more
-    // workgroups than CUs only multiplies the partial-sum traffic (147 KB per workgroup for a 64x64 tile)
-    // cu_limit: a weight gradient launched on a side stream beside the dgrad chain takes only part of the GPU (its persistent
-    // workgroups cannot share a CU with the chain's kernels, so a full-width launch makes the chain wait: tuning.py side_cus)
-    const int slots = p.cu_limit > 0 ? p.cu_limit : rd_switch("RD_WG_SLOTS", rd_num_cus());
-    int gx = (slots + pairs - 1) / pairs;
-    if (gx > g.total_tiles) gx = g.total_tiles;
-    if (gx < 1) gx = 1;
-    g.gx = gx;
-    g.nsplit = gx;
-    return g;
+// launched with the rd_wgrad_t that holds partial, dW and beta
+template <auto K> void reduce_thunk(const Route& r, const void* wgrad, const void*, hipStream_t st) {
+    const rd_wgrad_t& w = *static_cast<const rd_wgrad_t*>(wgrad);
+    const int* a = r.v.iarg;
+    rd_launch(K, rd_route_grid(r), dim3(r.v.block), (size_t)r.v.lds, st, (const float*)w.partial, w.dW, a[0], a[1], a[2], a[3], a[4], a[5], w.beta);
 }
-
-template <typename T, int TAPS, int MB, int NB>
-int launch_wgrad(const rd_wgrad_t& p, const WgradGeom& g, hipStream_t st) {
-    constexpr int HALO = (TAPS == 9) ? 1 : 0;
-    constexpr int PH = TH + 2 * HALO, PW = TW + 2 * HALO;
-    size_t lds = (size_t)(PH * PW * NB * 32 + TH * TW * MB * 32) * sizeof(T);
-    const size_t lds_red = (size_t)(4 / (MB * NB) - 1) * (MB * NB) * 16 * 64 * sizeof(float);
-    if (lds < lds_red) lds = lds_red;
-    dim3 grid(g.gx, g.CoutPadW / (MB * 32), g.CinPadW / (NB * 32));
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, TAPS, MB, NB>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    rd_launch((wgrad_kernel<T, TAPS, MB, NB>), grid, dim3(256), lds, st, p, g.CoutPadW, g.CinPadW, g.total_tiles, rdfin::current());
-    return (int)hipGetLastError();
-}
-
-template <int TAPS>
-int launch_wgrad_c16(const rd_wgrad_t& p, const WgradGeom& g, hipStream_t st) {
-    constexpr int HALO = (TAPS == 9) ? 1 : 0;
-    dim3 grid(g.gx, g.CoutPadW / 16, g.CinPadW / 16);
-    size_t lds = (size_t)((TH + 2 * HALO) * (TW + 2 * HALO) + 4) * 48 + (size_t)TH * TW * 48;
-    const size_t lds_red = (size_t)3 * TAPS * 4 * 64 * sizeof(float);
-    if (lds < lds_red) lds = lds_red;
-    if (p.dz.mode == RD_SRC_BNBWD)
-        rd_launch((wgrad_c16_tr_kernel<TAPS, 2>), grid, dim3(256), lds, st, p, g.CoutPadW, g.CinPadW, g.total_tiles, rdfin::current());
-    else
-        rd_launch((wgrad_c16_tr_kernel<TAPS, 1>), grid, dim3(256), lds, st, p, g.CoutPadW, g.CinPadW, g.total_tiles, rdfin::current());
-    return (int)hipGetLastError();
-}
-
-template <int TAPS, int MB, int NB>
-int launch_wgrad_tr(const rd_wgrad_t& p, const WgradGeom& g, hipStream_t st) {
-    constexpr int HALO = (TAPS == 9) ? 1 : 0;
-    constexpr int PH = TH + 2 * HALO, PW = TW + 2 * HALO;
-    size_t lds = (size_t)(PH * PW + 4) * tr_pitch(NB * 32) + (size_t)TH * TW * tr_pitch(MB * 32);
-    const size_t lds_red = (size_t)(4 / (MB * NB) - 1) * (MB * NB) * 16 * 64 * sizeof(float);
-    if (lds < lds_red) lds = lds_red;
-    dim3 grid(g.gx, g.CoutPadW / (MB * 32), g.CinPadW / (NB * 32));
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_tr_kernel<TAPS, MB, NB, 1, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_tr_kernel<TAPS, MB, NB, 2, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_tr_kernel<TAPS, MB, NB, 1, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    if constexpr (TAPS == 9 && MB == 2 && NB == 2) {
-        if (g.sym) return rd_wgrad_sym_launch(p, g.gx, g.CoutPadW, g.CinPadW, st);
-        // 64 x 64 blocks, plain sources: the warp-specialised kernel (4-row LDS tiles: twice the tile count)
-        static const int ws = rd_switch("RD_WG_WS", 1);
-        if (ws && wgrad_pf_ok(p)) {
-            const int ws_lds = 2 * ((6 * PW + 4) * tr_pitch(64) + 4 * TW * tr_pitch(64) + 256 * 16) + p.G * 2 * 3 * 64 * (int)sizeof(float);
-            const int tiles_ws = p.N * ((p.H + 3) / 4) * ((p.W + TW - 1) / TW);
-#define RD_WGWS_LAUNCH(NQZ, XP) do { \
-                static int attr_lds = 0; \
-                if (attr_lds < ws_lds) { \
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ws_kernel<NQZ, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, ws_lds); \
-                    attr_lds = ws_lds; \
-                } \
-                rd_launch((wgrad_ws_kernel<NQZ, XP>), grid, dim3(512), ws_lds, st, p, g.CoutPadW, g.CinPadW, tiles_ws, rdfin::current()); \
-                return (int)hipGetLastError(); \
-            } while (0)
+rd_kernel_t reduce_kernels[3] = {RD_KERNEL(reduce_thunk, 0, wgrad_reduce_kernel<8, 1>), RD_KERNEL(reduce_thunk, 0, wgrad_reduce_kernel<32, 4>),
+                                 RD_KERNEL(reduce_thunk, 0, wgrad_reduce_kernel<32, 1>)};
+// wgrad_c16_tr_kernel<TAPS, NQZ>: c16_kernels[1x1][dz plain]
+rd_kernel_t c16_kernels[2][2] = {{RD_KERNEL(rd_thunk_wgrad, 0, wgrad_c16_tr_kernel<9, 2>), RD_KERNEL(rd_thunk_wgrad, 0, wgrad_c16_tr_kernel<9, 1>)},
+                                 {RD_KERNEL(rd_thunk_wgrad, 0, wgrad_c16_tr_kernel<1, 2>), RD_KERNEL(rd_thunk_wgrad, 0, wgrad_c16_tr_kernel<1, 1>)}};
+// The transpose-read kernels, one row per block shape: tr_kernels[1x1][MB == 1][NB == 1][column].  Columns 0-2 are
+// wgrad_tr_kernel<TAPS, MB, NB, NQZ, PF> for plain sources / a BatchNorm-backward dz / sources that need the generic loader; the 3x3 row of
+// 64 x 64 blocks also has the warp-specialised wgrad_ws_kernel<NQZ, XP> in columns TR_WS, TR_WS + 1 (XP 0, dz BatchNorm-backward / plain), preceded
+// (debug build, columns 3-7) by the timing experiments RD_WGWS_EXP selects.
+#define RD_TR(...) RD_KERNEL(rd_thunk_wgrad, RD_ATTR_LDS, __VA_ARGS__)
+#define RD_TR_ROW(TAPS, MB, NB) RD_TR(wgrad_tr_kernel<TAPS, MB, NB, 1, true>), RD_TR(wgrad_tr_kernel<TAPS, MB, NB, 2, true>), RD_TR(wgrad_tr_kernel<TAPS, MB, NB, 1, false>)
 #ifdef RD_DEBUG_SWITCHES
-            if (p.dz.mode == RD_SRC_BNBWD && rd_switch("RD_WGWS_EXP", 0) == 8) RD_WGWS_LAUNCH(2, 8);
-            if (p.dz.mode == RD_SRC_BNBWD && rd_switch("RD_WGWS_EXP", 0) == 9) RD_WGWS_LAUNCH(2, 1);
-            if (p.dz.mode == RD_SRC_BNBWD && rd_switch("RD_WGWS_EXP", 0) == 4) RD_WGWS_LAUNCH(1, 4);     // one operand, no transform: "both operands stored"
-
-            if (p.dz.mode != RD_SRC_BNBWD) {
-                switch (rd_switch("RD_WGWS_EXP", 0)) {
-                case 1: RD_WGWS_LAUNCH(1, 1);
-                case 4: RD_WGWS_LAUNCH(1, 4);
-                case 5: RD_WGWS_LAUNCH(1, 5);
-                default: break;
-                }
-            }
+constexpr int TR_WS = 8;
+#define RD_TR_WS_EXP RD_TR(wgrad_ws_kernel<2, 8>), RD_TR(wgrad_ws_kernel<2, 1>), RD_TR(wgrad_ws_kernel<1, 4>), RD_TR(wgrad_ws_kernel<1, 1>), RD_TR(wgrad_ws_kernel<1, 5>),
+#else
+constexpr int TR_WS = 3;
+#define RD_TR_WS_EXP
 #endif
-            if (p.dz.mode == RD_SRC_BNBWD) RD_WGWS_LAUNCH(2, 0);
-            RD_WGWS_LAUNCH(1, 0);
-#undef RD_WGWS_LAUNCH
-        }
-    }
-    if (!wgrad_pf_ok(p))
-        rd_launch((wgrad_tr_kernel<TAPS, MB, NB, 1, false>), grid, dim3(256), lds, st, p, g.CoutPadW, g.CinPadW, g.total_tiles, rdfin::current());
-    else if (p.dz.mode == RD_SRC_BNBWD)
-        rd_launch((wgrad_tr_kernel<TAPS, MB, NB, 2, true>), grid, dim3(256), lds, st, p, g.CoutPadW, g.CinPadW, g.total_tiles, rdfin::current());
-    else
-        rd_launch((wgrad_tr_kernel<TAPS, MB, NB, 1, true>), grid, dim3(256), lds, st, p, g.CoutPadW, g.CinPadW, g.total_tiles, rdfin::current());
-    return (int)hipGetLastError();
-}
-
-template <typename T>
-int dispatch_wgrad(const rd_wgrad_t& p, hipStream_t st) {
-    const WgradGeom g = wgrad_geom<T>(p);
-    int e;
-    if (g.c16) {
-        e = p.taps == 9 ? launch_wgrad_c16<9>(p, g, st) : launch_wgrad_c16<1>(p, g, st);
-    } else if (sizeof(T) == 2 && wgrad_slots_ok(p) && rd_switch("RD_WG_TR_OFF", 0) == 0) {
-        // bf16, every source made of whole 16-byte channel slots: [pixel][channel] LDS tiles + ds_read_b64_tr_b16
-#define RD_WGT(TAPS_)                                                                \
-    if (g.MB == 2 && g.NB == 2) e = launch_wgrad_tr<TAPS_, 2, 2>(p, g, st);          \
-    else if (g.MB == 2) e = launch_wgrad_tr<TAPS_, 2, 1>(p, g, st);                  \
-    else if (g.NB == 2) e = launch_wgrad_tr<TAPS_, 1, 2>(p, g, st);                  \
-    else e = launch_wgrad_tr<TAPS_, 1, 1>(p, g, st);
-        if (p.taps == 9) { RD_WGT(9) } else { RD_WGT(1) }
-#undef RD_WGT
-    } else {
-        // fp32, and bf16 with ragged channel counts (e.g. a 3-channel image that is not padded to a slot)
-#define RD_WG(TAPS_)                                                                 \
-    if (g.MB == 2 && g.NB == 2) e = launch_wgrad<T, TAPS_, 2, 2>(p, g, st);          \
-    else if (g.MB == 2) e = launch_wgrad<T, TAPS_, 2, 1>(p, g, st);                  \
-    else if (g.NB == 2) e = launch_wgrad<T, TAPS_, 1, 2>(p, g, st);                  \
-    else e = launch_wgrad<T, TAPS_, 1, 1>(p, g, st);
-        if (p.taps == 9) { RD_WG(9) } else { RD_WG(1) }
-#undef RD_WG
-    }
-    if (e) return e;
-    if (rd_switch("RD_WG_NO_REDUCE", 0)) return 0;          // debug build only: timing experiment (what the split reductions cost the step)
-    return rd_wgrad_reduce_launch(p.partial, p.dW, g.nsplit, p.taps, p.Cout, p.Cin, g.CoutPadW, g.CinPadW, p.beta, st);
-}
+rd_kernel_t tr_kernels[2][2][2][TR_WS + 2] = {
+    {{{RD_TR_ROW(9, 2, 2), RD_TR_WS_EXP RD_TR(wgrad_ws_kernel<2, 0>), RD_TR(wgrad_ws_kernel<1, 0>)}, {RD_TR_ROW(9, 2, 1)}}, {{RD_TR_ROW(9, 1, 2)}, {RD_TR_ROW(9, 1, 1)}}},
+    {{{RD_TR_ROW(1, 2, 2)}, {RD_TR_ROW(1, 2, 1)}}, {{RD_TR_ROW(1, 1, 2)}, {RD_TR_ROW(1, 1, 1)}}}};
+#undef RD_TR_WS_EXP
+#undef RD_TR_ROW
+// wgrad_kernel<T, TAPS, MB, NB>: plain_kernels[fp32][1x1][MB == 1][NB == 1]
+#define RD_WG_ROW(T, TAPS) {{RD_TR(wgrad_kernel<T, TAPS, 2, 2>), RD_TR(wgrad_kernel<T, TAPS, 2, 1>)}, {RD_TR(wgrad_kernel<T, TAPS, 1, 2>), RD_TR(wgrad_kernel<T, TAPS, 1, 1>)}}
+rd_kernel_t plain_kernels[2][2][2][2] = {{RD_WG_ROW(bf16_t, 9), RD_WG_ROW(bf16_t, 1)}, {RD_WG_ROW(float, 9), RD_WG_ROW(float, 1)}};
+#undef RD_WG_ROW
+#undef RD_TR
 
 }  // namespace
 
-int rd_wgrad_reduce_launch(const float* partial, float* dW, int nsplit, int taps, int Cout, int Cin, int CoutPadW, int CinPadW, float beta,
-                           hipStream_t st) {
+void rd_route_wgrad_reduce(const float* partial, int nsplit, int taps, int Cout, int Cin, int CoutPadW, int CinPadW, Route& r) {
     const int total = taps * Cout * Cin;
     // many splits of a small filter (the 16/32-channel layers): 8 outputs x 32 split lanes per block, scalar loads -- 32 loads per output
     // are in flight there already, and four outputs per thread would leave a quarter of the blocks (measured: 10.7 -> 13.2 us)
     if (nsplit >= 128 && total <= 16384) {
-        rd_launch((wgrad_reduce_kernel<8, 1>), dim3((total + 7) / 8), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
+        rd_route_set(r, reduce_kernels[0], (total + 7) / 8, 1, 1, 256, 0);
     } else {
         // 8 split lanes: a thread has one or two loads in flight with few splits -> whole float4 columns when Cin % 4 == 0 (CinPadW, hence
         // every row and split of the partials, is a multiple of 16 floats).  RD_WG_REDUCE_V4=0 (debug library): the scalar form everywhere
         const bool v4 = Cin % 4 == 0 && (((uintptr_t)partial) & 15) == 0 && rd_switch("RD_WG_REDUCE_V4", 1);
-        int blocks = v4 ? (total + 127) / 128 : (total + 31) / 32;
-        if (blocks > 8192) blocks = 8192;
-        if (v4) rd_launch((wgrad_reduce_kernel<32, 4>), dim3(blocks), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
-        else rd_launch((wgrad_reduce_kernel<32, 1>), dim3(blocks), dim3(256), 0, st, partial, dW, nsplit, taps, Cout, Cin, CoutPadW, CinPadW, beta);
+        const int blocks = v4 ? (total + 127) / 128 : (total + 31) / 32;
+        rd_route_set(r, reduce_kernels[v4 ? 1 : 2], blocks > 8192 ? 8192 : blocks, 1, 1, 256, 0);
     }
-    return (int)hipGetLastError();
+    const int a[6] = {nsplit, taps, Cout, Cin, CoutPadW, CinPadW};
+    for (int i = 0; i < 6; ++i) r.v.iarg[i] = a[i];
 }
 
-int rd_wgrad_dispatch(const rd_wgrad_t& p, int dtype, hipStream_t st) {
-    return dtype == RD_BF16 ? dispatch_wgrad<bf16_t>(p, st) : dispatch_wgrad<float>(p, st);
+// The family order of rd_wgrad: 16 x 16 blocks -> the symmetric 128 x 64 kernel -> the warp-specialised 64 x 64 kernel -> the transpose-read
+// kernels -> wgrad_kernel.  Every weight-gradient kernel writes partial[nsplit = grid.x][taps][CoutPadW][CinPadW] (iarg 0, 1 of out[0]);
+// out[1] reduces them into dW.
+int rd_wgrad_route_plan(const rd_wgrad_t& p, int dtype, Route out[2]) {
+    const bool bf = dtype == RD_BF16, pf_ok = wgrad_pf_ok(p), tr_on = rd_switch("RD_WG_TR_OFF", 0) == 0;
+    const int HALO = (p.taps == 9) ? 1 : 0, PH = TH + 2 * HALO, PW = TW + 2 * HALO;
+    const int total_tiles = p.N * ((p.H + TH - 1) / TH) * ((p.W + TW - 1) / TW);
+    const int t1 = p.taps != 9, nqz = p.dz.mode == RD_SRC_BNBWD ? 2 : 1;
+    Route& r = out[0];
+    int CoutPadW, CinPadW;
+    // 16 x 16 blocks (v_mfma_f32_16x16x32_bf16, 3 workgroups/CU): the 16-channel layers, and -- a grid of such blocks,
+    // transpose-read kernel only -- the layers with <= 16 output channels on 32 input channels (dec.out1 32->2,
+    // dec.convu1.conv2 32->16, rec.convu1.conv1 32->16), which would leave half of every 32 x 32 block's rows empty
+    if (bf && p.Cout <= 16 && p.Cin <= (rd_switch("RD_WG_C16_GRID", 1) ? 32 : 16) && pf_ok && tr_on) {
+        CoutPadW = 16;
+        CinPadW = (p.Cin + 15) / 16 * 16;
+        // exactly the resident set (no second, partially filled round) at 3 workgroups/CU
+        // (cu_limit does not apply: these layers are the 400x400 / 200x200 ones, HBM-bound, and want every CU's load path)
+        int gx = 3 * rd_num_cus() / (CinPadW / 16);
+        if (gx > total_tiles) gx = total_tiles;
+        size_t lds = (size_t)(PH * PW + 4) * 48 + (size_t)TH * TW * 48;
+        const size_t lds_red = (size_t)3 * p.taps * 4 * 64 * sizeof(float);
+        rd_route_set(r, c16_kernels[t1][nqz == 1], gx < 1 ? 1 : gx, 1, CinPadW / 16, 256, lds < lds_red ? lds_red : lds);
+        r.v.iarg[2] = total_tiles;
+    } else {
+        const int cout32 = (p.Cout + 31) / 32, cin32 = (p.Cin + 31) / 32;
+        // fp32 keeps 32x32 blocks (LDS budget); bf16 uses 64-wide tiles where the layer has them
+        const int MB = (bf && cout32 % 2 == 0 && rd_switch("RD_WG_MB_MAX", 2) >= 2) ? 2 : 1;
+        const int NB = (bf && cin32 % 2 == 0 && rd_switch("RD_WG_NB_MAX", 2) >= 2) ? 2 : 1;
+        CoutPadW = cout32 * 32;
+        CinPadW = cin32 * 32;
+        int pairs = (CoutPadW / (MB * 32)) * (CinPadW / (NB * 32));
+        const bool wide = bf && p.taps == 9 && MB == 2 && NB == 2 && pf_ok && tr_on && rd_switch("RD_WG_WS", 1);
+        // 3x3 layers with whole 128-channel blocks of gradient channels on plain sources: the symmetric eight-wave kernel, half as many
+        // workgroups per pixel split (each owns 128 x 64 channels), so twice the splits on the same compute-unit budget
+        const bool sym = wide && CoutPadW % 128 == 0 && p.G * (2 * 64 + 3 * 128) * 4 <= 16384 && (p.na == 1 || p.a[0].C % 64 == 0) &&
+                         rd_switch("RD_WG_SYM", RD_WG_SYM_DEFAULT);
+        if (sym) pairs /= 2;
+        // these kernels hold 144 accumulator registers per lane -> one workgroup per CU is resident: launching more
+        // workgroups than CUs only multiplies the partial-sum traffic (147 KB per workgroup for a 64x64 tile)
+        // cu_limit: a weight gradient launched on a side stream beside the dgrad chain takes only part of the GPU (its persistent
+        // workgroups cannot share a CU with the chain's kernels, so a full-width launch makes the chain wait: tuning.py side_cus)
+        const int slots = p.cu_limit > 0 ? p.cu_limit : rd_switch("RD_WG_SLOTS", rd_num_cus());
+        int gx = (slots + pairs - 1) / pairs;
+        if (gx > total_tiles) gx = total_tiles;
+        if (gx < 1) gx = 1;
+        const int gy = CoutPadW / (MB * 32), gz = CinPadW / (NB * 32);
+        const size_t lds_red = (size_t)(4 / (MB * NB) - 1) * (MB * NB) * 16 * 64 * sizeof(float);
+        rd_kernel_t* row = tr_kernels[t1][MB == 1][NB == 1];
+        if (sym) {
+            rd_route_wgrad_sym(p, gx, CoutPadW, CinPadW, r);
+        } else if (wide) {
+            // 64 x 64 blocks, plain sources: the warp-specialised kernel (4-row LDS tiles: twice the tile count)
+            int col = TR_WS + (nqz == 1);
+#ifdef RD_DEBUG_SWITCHES
+            // timing experiments: XP 8 / 1 on a BatchNorm-backward dz (RD_WGWS_EXP 8 / 9), XP 1 / 5 on a plain dz, XP 4 ("both operands stored":
+            // one operand, no transform) on either
+            const int xp = rd_switch("RD_WGWS_EXP", 0);
+            const int exp_col = nqz == 2 ? (xp == 8 ? 3 : xp == 9 ? 4 : xp == 4 ? 5 : 0) : (xp == 1 ? 6 : xp == 4 ? 5 : xp == 5 ? 7 : 0);
+            if (exp_col) col = exp_col;
+#endif
+            rd_route_set(r, row[col], gx, gy, gz, 512,
+                         2 * ((6 * PW + 4) * tr_pitch(64) + 4 * TW * tr_pitch(64) + 256 * 16) + p.G * 2 * 3 * 64 * (int)sizeof(float));
+            r.v.iarg[2] = p.N * ((p.H + 3) / 4) * ((p.W + TW - 1) / TW);
+        } else if (bf && wgrad_slots_ok(p) && tr_on) {
+            // bf16, every source made of whole 16-byte channel slots: [pixel][channel] LDS tiles + ds_read_b64_tr_b16
+            const size_t lds = (size_t)(PH * PW + 4) * tr_pitch(NB * 32) + (size_t)TH * TW * tr_pitch(MB * 32);
+            rd_route_set(r, row[!pf_ok ? 2 : nqz == 2 ? 1 : 0], gx, gy, gz, 256, lds < lds_red ? lds_red : lds);
+            r.v.iarg[2] = total_tiles;
+        } else {
+            // fp32, and bf16 with ragged channel counts (e.g. a 3-channel image that is not padded to a slot)
+            const size_t lds = (size_t)(PH * PW * NB * 32 + TH * TW * MB * 32) * (bf ? 2 : 4);
+            rd_route_set(r, plain_kernels[!bf][t1][MB == 1][NB == 1], gx, gy, gz, 256, lds < lds_red ? lds_red : lds);
+            r.v.iarg[2] = total_tiles;
+        }
+    }
+    r.v.iarg[0] = CoutPadW;
+    r.v.iarg[1] = CinPadW;
+    if (rd_switch("RD_WG_NO_REDUCE", 0)) return 1;          // debug build only: timing experiment (what the split reductions cost the step)
+    rd_route_wgrad_reduce(p.partial, r.v.grid[0], p.taps, p.Cout, p.Cin, CoutPadW, CinPadW, out[1]);
+    return 2;
 }
-
-int64_t rd_wgrad_ws_bytes(const rd_wgrad_t& p, int dtype) {
-    const WgradGeom g = dtype == RD_BF16 ? wgrad_geom<bf16_t>(p) : wgrad_geom<float>(p);
-    return (int64_t)g.nsplit * p.taps * g.CoutPadW * g.CinPadW * (int64_t)sizeof(float);
-}
-
 
 #ifdef RD_DEBUG_SWITCHES
 extern "C" int rd_debug_wg_trace(int key, unsigned long long* out) {       // debug library only: arm (out == null) or read 2 x 64 x 4 stamps

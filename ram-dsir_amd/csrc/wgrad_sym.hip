@@ -1,5 +1,5 @@
 // wgrad_sym.hip -- weight gradient of the 3x3 layers with whole 128-channel blocks of gradient channels (bf16, plain sources): 128 x 64
-// channel blocks of dW per workgroup on eight symmetric waves.  Dispatched by wgrad.hip (wgrad_geom: `sym`), reduced by its
+// channel blocks of dW per workgroup on eight symmetric waves.  Routed by wgrad.hip (rd_wgrad_route_plan: `sym`), reduced by its
 // wgrad_reduce_kernel.  cuDNN's wgrad behind /root/reference/code/networks/unet.py:37-43,81-88 (ConvD / ConvU convs, backward).
 #include "conv_device.h"
 #include "conv_dispatch.h"
@@ -353,22 +353,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_sym_kernel(const rd_wgrad_t p, i
         }
 }
 
+rd_kernel_t sym_kernels[2] = {RD_KERNEL(rd_thunk_wgrad, RD_ATTR_LDS, wgrad_sym_kernel<1>), RD_KERNEL(rd_thunk_wgrad, RD_ATTR_LDS, wgrad_sym_kernel<2>)};
+
 }  // namespace
 
-int rd_wgrad_sym_launch(const rd_wgrad_t& p, int gx, int CoutPadW, int CinPadW, hipStream_t st) {
+void rd_route_wgrad_sym(const rd_wgrad_t& p, int gx, int CoutPadW, int CinPadW, Route& r) {
     constexpr int PW = TW + 2;
     const int sym_lds = 2 * ((6 * PW + 4) * tr_pitch(64) + 2 * 4 * TW * tr_pitch(64) + 512 * 16) + p.G * (2 * 64 + 3 * 128) * (int)sizeof(float) + 16;
-    const int tiles_sym = p.N * ((p.H + 3) / 4) * ((p.W + TW - 1) / TW);
-    const dim3 sgrid(gx, CoutPadW / 128, CinPadW / 64);
-    static int sym_attr = 0;
-    if (sym_attr < sym_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_sym_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, sym_lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_sym_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, sym_lds);
-        sym_attr = sym_lds;
-    }
-    if (p.dz.mode == RD_SRC_BNBWD)
-        rd_launch((wgrad_sym_kernel<2>), sgrid, dim3(512), sym_lds, st, p, CoutPadW, CinPadW, tiles_sym, rdfin::current());
-    else
-        rd_launch((wgrad_sym_kernel<1>), sgrid, dim3(512), sym_lds, st, p, CoutPadW, CinPadW, tiles_sym, rdfin::current());
-    return (int)hipGetLastError();
+    rd_route_set(r, sym_kernels[p.dz.mode == RD_SRC_BNBWD], gx, CoutPadW / 128, CinPadW / 64, 512, sym_lds);
+    r.v.iarg[2] = p.N * ((p.H + 3) / 4) * ((p.W + TW - 1) / TW);
 }

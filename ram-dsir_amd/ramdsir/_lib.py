@@ -43,6 +43,11 @@ class RdWgrad(C.Structure):
                 ('beta', f32), ('cu_limit', i32)]
 
 
+class RdRoute(C.Structure):
+    """rd_route_t (include/ramdsir.h): one launch an entry point would make."""
+    _fields_ = [('kernel', C.c_char_p), ('grid', i32 * 3), ('block', i32), ('lds', i32), ('iarg', i32 * 6), ('stores_sources', i32)]
+
+
 class RdBnFwd(C.Structure):
     _fields_ = [('stats', fp), ('conv_bias', fp), ('scale', fp), ('shift', fp), ('mean', fp), ('invstd', fp), ('gamma', fp * MAXG),
                 ('beta', fp * MAXG), ('running_mean', fp * MAXG), ('running_var', fp * MAXG),
@@ -156,6 +161,9 @@ _SIGS = {
     'rd_wgrad': (C.c_int, [C.POINTER(RdWgrad), C.c_int, vp]),
     'rd_wgrad_reduce': (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
     'rd_conv_honours_src_out': (C.c_int, [C.POINTER(RdConv), C.c_int]),
+    'rd_conv_route': (C.c_int, [C.POINTER(RdConv), C.c_int, C.POINTER(RdRoute)]),
+    'rd_wgrad_route': (C.c_int, [C.POINTER(RdWgrad), C.c_int, C.POINTER(RdRoute)]),
+    'rd_conv_bwd_fused_route': (C.c_int, [C.POINTER(RdConv), C.POINTER(RdWgrad), C.c_int, C.POINTER(RdRoute)]),
     'rd_conv_bwd_fused_ok': (C.c_int, [C.POINTER(RdConv), C.POINTER(RdWgrad), C.c_int]),
     'rd_conv_bwd_fused_workspace': (i64, [C.POINTER(RdConv), C.POINTER(RdWgrad), C.c_int]),
     'rd_conv_bwd_fused': (C.c_int, [C.POINTER(RdConv), C.POINTER(RdWgrad), C.c_int, vp]),

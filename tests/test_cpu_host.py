@@ -36,7 +36,7 @@ def test_ctypes_struct_sizes_match_the_c_compiler(tmp_path):
     from ramdsir import _lib as L
     names = {'rd_src_t': L.RdSrc, 'rd_dst_t': L.RdDst, 'rd_conv_t': L.RdConv, 'rd_wgrad_t': L.RdWgrad, 'rd_bn_fwd_t': L.RdBnFwd,
              'rd_bn_bwd_t': L.RdBnBwd, 'rd_seg_loss_t': L.RdSegLoss, 'rd_adam_t': L.RdAdam, 'rd_pack_entry_t': L.RdPackEntry,
-             'rd_ram_t': L.RdRam, 'rd_launch_t': L.RdLaunch}
+             'rd_ram_t': L.RdRam, 'rd_launch_t': L.RdLaunch, 'rd_route_t': L.RdRoute}
     src = '#include <stdio.h>\n#include "ramdsir.h"\nint main(){' + ''.join(
         'printf("%s %%zu\\n", sizeof(%s));' % (n, n) for n in names) + 'return 0;}'
     c = tmp_path / 's.c'

@@ -439,7 +439,7 @@ def test_exact_wgrad(case, dtype):
     _run_wgrad(case[0], dtype)
 
 
-# cu_limit -> pixel splits (csrc/wgrad.hip wgrad_geom): splits = ceil(cu_limit / blocks of the layer), at most the 8 x 32-tile count.
+# cu_limit -> pixel splits (csrc/wgrad.hip rd_wgrad_route_plan): splits = ceil(cu_limit / blocks of the layer), at most the 8 x 32-tile count.
 # The fp32 kernel deals 8 x 32 tiles; the bf16 kernels these cases take (wgrad_ws_kernel, wgrad_sym_kernel) deal 4 x 32 tiles.
 WG_CU_LIMITS = {
     # case: {dtype: (tiles the kernel deals, cu_limit that gives a split count which does not divide them)}

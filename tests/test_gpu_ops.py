@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from ramdsir import _lib as L          # noqa: E402
 import gpu_util as U                   # noqa: E402
+import forced_dispatch                  # noqa: E402
 
 DTYPES = ['f32', 'bf16']
 
@@ -370,7 +371,7 @@ def test_conv_gradient_also_stores_the_dz_it_forms():
     assert torch.isfinite(got).all()
     _assert_bf16_rounding_of(got, dz, (g * U.group_rows(P, gstart, N)).abs() + (z * U.group_rows(Q, gstart, N)).abs() + U.group_rows(R, gstart, N).abs(), 'dz')
     # the same gradient launch on a STORED dz (plain source): it runs on an instantiation that never writes rd_src_t.out, the query says so
-    # beforehand (one predicate for query and dispatch, csrc/conv_pp.hip rd_conv_ws_stores_sources) and the tensor is left alone
+    # beforehand (query and launch read one route, csrc/conv_pp.hip rd_route_ws) and the tensor is left alone
     src2 = U.make_src(keep, dz, L.SRC_RAW, dtype)
     untouched = torch.full((N, H, W, Cz), 7.0, dtype=torch.bfloat16, device=U.dev())
     src2.out = untouched.data_ptr()
@@ -957,22 +958,7 @@ def test_layout_boundary_kernels(dtype):
 
 
 # ------------------------------------------------------------------------------------ every 64-wide conv kernel
-@pytest.mark.parametrize('env', [
-    {'RD_CONV_WS': '3', 'RD_CONV_WS_MIN2': '0', 'RD_CONV_NB1_BELOW': '0'},          # conv_ws_kernel: forward AND gradient launches
-    {'RD_CONV_WS': '3', 'RD_CONV_WS_MIN2': '0', 'RD_CONV_NB1_BELOW': '0', 'RD_CONV_WS_FLAT': '0'},   # ... on 8 x 32 tiles only
-    {'RD_CONV_WS': '3', 'RD_CONV_WS_MIN2': '1073741824', 'RD_CONV_NB1_BELOW': '0'},  # conv_ws_kernel forward, gradients on conv_pf_kernel (the round-3 default)
-    {'RD_CONV_WS': '0', 'RD_CONV_PP_ALL': '1', 'RD_CONV_NB1_BELOW': '0'},           # conv_pp_kernel (LDS-staged epilogue) everywhere
-    {'RD_CONV_PP_OFF': '1', 'RD_CONV_NB1_BELOW': '0'},                              # conv_pf_kernel with the register epilogues
-    {'RD_CONV_PP_OFF': '1', 'RD_CONV_NB1_BELOW': '0', 'RD_CONV_FLAT_TILES': '0'},   # ... on 8 x 32 tiles only (default: 10 x 25 where more lanes are live)
-    {'RD_CONV_PP_OFF': '1', 'RD_CONV_PF_LEAN_OFF': '1', 'RD_CONV_NB1_BELOW': '0'},  # conv_pf_kernel with the LDS-staged epilogue
-    {'RD_CONV_NB1_BELOW': '100000'},                                                # 32-wide tiles for every 64-wide launch
-    {'RD_SW_TPW': '5'},                                                             # conv_small_fwd_kernel: 5 tiles per workgroup (+ ghosts)
-    {'RD_SW_TPW': '2'},                                                             # ... fewer tiles than register sets
-    {'RD_SW_NWV': '4'},                                                             # ... two 256-thread workgroups per CU, two tile rows per wave (<= 16-channel inputs)
-    {'RD_SW_NWV': '4', 'RD_SW_TPW': '5'},
-    {'RD_SW_NWV': '8'},                                                             # ... one 512-thread workgroup per CU for every input width
-    {'RD_CONV_SMALL_FWD': '0'},                                                      # conv_small_kernel for the forward launches
-], ids=['ws_fwd_bwd', 'ws_fwd_bwd_8x32', 'ws_fwd_pf_bwd', 'pp_staged', 'pf_lean', 'pf_lean_8x32', 'pf_staged', 'nb1_everywhere', 'small_fwd_tpw5', 'small_fwd_tpw2', 'small_fwd_nwv4', 'small_fwd_nwv4_tpw5', 'small_fwd_nwv8', 'small_fwd_off'])
+@pytest.mark.parametrize('env', forced_dispatch.ENVS, ids=forced_dispatch.IDS)
 def test_conv_kernels_under_forced_dispatch(env):
     """Which kernel a 64-wide launch takes depends on its size (csrc/conv_pp.hip, conv_big.hip), and the cases above are small.
     The dispatch switches (debug build of the library only) are read once per process: re-run the conv parity tests in a child
