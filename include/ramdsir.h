@@ -464,14 +464,20 @@ int rd_ram_mutate(const float* amp_src, const float* amp_trg, float* out, int C,
  * across their boundary (the data-parallel step joins the weight-gradient lane only in front of the optimizer);
  * rd_join_lanes makes streams[0] wait for every lane in `mask`.  Works eagerly and under stream capture (events only).
  * Returns 0, the first failing entry point's error code, or -1 for a malformed entry (its index in *bad_index if not NULL). */
-enum {
-    RD_OP_FORK = 1, RD_OP_JOIN = 2,
-    RD_OP_CONV = 10, RD_OP_WGRAD, RD_OP_CONV_BWD_FUSED, RD_OP_CONV_BWD_FUSED_REDUCE, RD_OP_PACK_WEIGHTS_BATCHED,
-    RD_OP_BN_FINALIZE_FWD, RD_OP_BN_FINALIZE_BWD, RD_OP_GN_FINALIZE_FWD, RD_OP_GN_FINALIZE_BWD,
-    RD_OP_UP_STATS, RD_OP_BN_STATS, RD_OP_UP_BWD, RD_OP_POOL_FWD, RD_OP_POOL_BWD, RD_OP_BN_APPLY,
-    RD_OP_NCHW_TO_NHWC, RD_OP_NHWC_TO_NCHW, RD_OP_GRAD_IN, RD_OP_COLSUM,
-    RD_OP_SEG_LOSS, RD_OP_REC_LOSS, RD_OP_ADAM_STEP, RD_OP_ZERO, RD_OP_RAM_MIX
-};
+/* The entry points a list can hold: X(enum suffix, entry point).  THE table: the RD_OP_* codes below, the argument unpacking of
+ * csrc/runlist.hip (from each function's own signature) and rd_op_code() all come from it.  The codes are ABI: rows are only appended. */
+#define RD_LAUNCH_OPS(X)                                                                                                          \
+    X(CONV, rd_conv) X(WGRAD, rd_wgrad) X(CONV_BWD_FUSED, rd_conv_bwd_fused) X(CONV_BWD_FUSED_REDUCE, rd_conv_bwd_fused_reduce)  \
+    X(PACK_WEIGHTS_BATCHED, rd_pack_weights_batched) X(BN_FINALIZE_FWD, rd_bn_finalize_fwd) X(BN_FINALIZE_BWD, rd_bn_finalize_bwd) \
+    X(GN_FINALIZE_FWD, rd_gn_finalize_fwd) X(GN_FINALIZE_BWD, rd_gn_finalize_bwd) X(UP_STATS, rd_up_stats) X(BN_STATS, rd_bn_stats) \
+    X(UP_BWD, rd_up_bwd) X(POOL_FWD, rd_pool_fwd) X(POOL_BWD, rd_pool_bwd) X(BN_APPLY, rd_bn_apply) X(NCHW_TO_NHWC, rd_nchw_to_nhwc) \
+    X(NHWC_TO_NCHW, rd_nhwc_to_nchw) X(GRAD_IN, rd_grad_in) X(COLSUM, rd_colsum) X(SEG_LOSS, rd_seg_loss) X(REC_LOSS, rd_rec_loss)  \
+    X(ADAM_STEP, rd_adam_step) X(ZERO, rd_zero) X(RAM_MIX, rd_ram_mix)
+#define RD_OP_ENUM_(suffix, fn) RD_OP_##suffix,
+enum { RD_OP_FORK = 1, RD_OP_JOIN = 2, RD_OP_BEFORE_FIRST_ = 9, RD_LAUNCH_OPS(RD_OP_ENUM_) RD_OP_END_ };   /* RD_OP_CONV = 10 ... RD_OP_RAM_MIX = 33 */
+#undef RD_OP_ENUM_
+/* the RD_OP_* code of an entry point by its name ("rd_conv" -> 10), -1 if a list cannot hold it.  Host logic only. */
+int rd_op_code(const char* entry_point);
 #define RD_LAUNCH_MAX_ARGS 18
 typedef struct {
     int32_t op;
@@ -499,6 +505,19 @@ void rd_run_list_fork_counts(long long* bound, long long* recorded);
 /* carries[i] = 1 for the entries of lane 0 that rd_run_list would launch with a fork's event bound to them (a RD_OP_FORK of a lane > 0,
  * or a lane entry with wait_main, follows before the main stream is given anything else or joins a lane).  Host logic only. */
 int rd_run_list_fork_plan(const rd_launch_t* ops, int n, unsigned char* carries);
+/* The walk of rd_run_list without streams and without launches: what it would do with a list over n_streams distinct streams, step by
+ * step and in order -- launch entry `index` on `lane` (carries: with a fork's event bound to it, as rd_run_list_fork_plan says), make
+ * streams[lane] wait for the main stream's position (RD_STEP_FORK: a fork, or the edge in front of a wait_main entry), make the main
+ * stream wait for streams[lane] (RD_STEP_JOIN).  steps has room for 2 * n; *open_lanes, *bad_index and the return value are the walk's
+ * (-1 with the index of a malformed entry: lane, nargs, unknown op, nargs other than the entry point's).  Host logic only. */
+enum { RD_STEP_LAUNCH = 0, RD_STEP_FORK = 1, RD_STEP_JOIN = 2 };
+typedef struct {
+    int32_t kind;
+    int32_t lane;
+    int32_t index;      /* RD_STEP_LAUNCH: the entry; -1 otherwise */
+    int32_t carries;
+} rd_step_t;
+int rd_run_list_schedule(const rd_launch_t* ops, int n, int n_streams, uint32_t* open_lanes, int* bad_index, rd_step_t* steps, int* n_steps);
 
 /* ------------------------------------------------------------------------------------------------
  * GPU-resident training data (train.py --gpu_data, ramdsir/gpu_data.py): the decoded pixels of every image training can touch

@@ -8,6 +8,10 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <vector>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 #include "common.h"
 #include "../../include/ramdsir.h"
 
@@ -53,25 +57,8 @@ int edge(hipStream_t from, hipStream_t to) {
     return 0;
 }
 
-inline float as_f(uint64_t v) {
-    const uint32_t u = (uint32_t)v;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
 #ifdef RD_DEBUG_SWITCHES
 static int rd_switch_rl(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
-#endif
-
-#define P(i) ((void*)(uintptr_t)o.a[i])
-#define CP(T, i) ((const T*)(uintptr_t)o.a[i])
-#define I(i) ((int)(int64_t)o.a[i])
-#define L64(i) ((int64_t)o.a[i])
-#define F(i) (as_f(o.a[i]))
-#define NARGS(k) do { if (o.nargs != (k)) return -1; } while (0)
-
-#ifdef RD_DEBUG_SWITCHES
 // Debug library, RD_POISON_LDS=1: in front of EVERY launch of a list a kernel fills the LDS of every CU (and the registers of the waves
 // it runs) with a NaN pattern -- 0x7fc07fc0 is a NaN as fp32 and as two bf16, and 1e307-sized as half an fp64.  LDS and registers are
 // not cleared between kernels: a launch that reads either before writing it normally sees what the previous kernel of the same process
@@ -99,51 +86,42 @@ void poison_lds(void* st) {
 }
 #endif
 
+// One argument of an entry point from the 64-bit word rd_launch_t.a[] carries: pointers and integers as they are, a float from its bit
+// pattern in the low 32 bits.
+template <class T> T unpack(uint64_t v) {
+    static_assert(std::is_pointer_v<T> || std::is_same_v<T, int> || std::is_same_v<T, int64_t> || std::is_same_v<T, float>);
+    if constexpr (std::is_pointer_v<T>) return (T)(uintptr_t)v;
+    else if constexpr (std::is_same_v<T, float>) return __builtin_bit_cast(float, (uint32_t)v);
+    else return (T)(int64_t)v;
+}
+// One row per entry point of RD_LAUNCH_OPS (include/ramdsir.h): argument types and arity are the function's own signature minus the
+// trailing stream.
+struct OpRow {
+    const char* name;
+    int nargs;
+    int (*call)(const uint64_t* a, void* st);
+};
+template <class... P, size_t... I> int unpack_and_call(int (*fn)(P...), const uint64_t* a, void* st, std::index_sequence<I...>) {
+    static_assert(sizeof...(I) <= RD_LAUNCH_MAX_ARGS && std::is_same_v<std::tuple_element_t<sizeof...(I), std::tuple<P...>>, void*>);
+    return fn(unpack<std::tuple_element_t<I, std::tuple<P...>>>(a[I])..., st);
+}
+template <class... P> constexpr int arity(int (*)(P...)) { return (int)sizeof...(P) - 1; }
+template <auto Fn> int thunk(const uint64_t* a, void* st) { return unpack_and_call(Fn, a, st, std::make_index_sequence<arity(Fn)>{}); }
+#define RD_OP_ROW(suffix, fn) {#fn, arity(&fn), thunk<&fn>},
+constexpr OpRow OPS[] = {RD_LAUNCH_OPS(RD_OP_ROW)};
+static_assert(RD_OP_CONV == 10 && RD_OP_RAM_MIX == 33 && RD_OP_END_ - RD_OP_CONV == sizeof(OPS) / sizeof(OPS[0]), "the op codes are ABI");
+
+// the entry's row; null for an unknown op or a wrong argument count
+const OpRow* row_of(const rd_launch_t& o) {
+    const bool known = o.op >= RD_OP_CONV && o.op < RD_OP_END_ && o.nargs == OPS[o.op - RD_OP_CONV].nargs;
+    return known ? &OPS[o.op - RD_OP_CONV] : nullptr;
+}
 int call(const rd_launch_t& o, void* st) {
 #ifdef RD_DEBUG_SWITCHES
     poison_lds(st);
 #endif
-    switch (o.op) {
-    case RD_OP_CONV: NARGS(2); return rd_conv(CP(rd_conv_t, 0), I(1), st);
-    case RD_OP_WGRAD: NARGS(2); return rd_wgrad(CP(rd_wgrad_t, 0), I(1), st);
-    case RD_OP_CONV_BWD_FUSED: NARGS(3); return rd_conv_bwd_fused(CP(rd_conv_t, 0), CP(rd_wgrad_t, 1), I(2), st);
-    case RD_OP_CONV_BWD_FUSED_REDUCE: NARGS(3); return rd_conv_bwd_fused_reduce(CP(rd_conv_t, 0), CP(rd_wgrad_t, 1), I(2), st);
-    case RD_OP_PACK_WEIGHTS_BATCHED: NARGS(6); return rd_pack_weights_batched(CP(float, 0), P(1), CP(rd_pack_entry_t, 2), I(3), L64(4), I(5), st);
-    case RD_OP_BN_FINALIZE_FWD: NARGS(1); return rd_bn_finalize_fwd(CP(rd_bn_fwd_t, 0), st);
-    case RD_OP_BN_FINALIZE_BWD: NARGS(1); return rd_bn_finalize_bwd(CP(rd_bn_bwd_t, 0), st);
-    case RD_OP_GN_FINALIZE_FWD: NARGS(1); return rd_gn_finalize_fwd(CP(rd_bn_fwd_t, 0), st);
-    case RD_OP_GN_FINALIZE_BWD: NARGS(1); return rd_gn_finalize_bwd(CP(rd_bn_bwd_t, 0), st);
-    case RD_OP_UP_STATS: NARGS(11); return rd_up_stats(P(0), (double*)P(1), P(2), I(3), I(4), I(5), I(6), I(7), CP(int32_t, 8), I(9), I(10), st);
-    case RD_OP_BN_STATS: NARGS(9); return rd_bn_stats(P(0), (double*)P(1), I(2), I(3), I(4), I(5), I(6), CP(int32_t, 7), I(8), st);
-    case RD_OP_UP_BWD:
-        NARGS(15);
-        return rd_up_bwd(P(0), P(1), P(2), CP(float, 3), CP(float, 4), CP(float, 5), I(6), I(7), I(8), I(9), I(10), CP(int32_t, 11), I(12), CP(rd_bn_bwd_t, 13), I(14), st);
-    case RD_OP_POOL_FWD:
-        NARGS(14);
-        return rd_pool_fwd(P(0), CP(float, 1), CP(float, 2), F(3), P(4), I(5), I(6), I(7), I(8), I(9), CP(int32_t, 10), I(11), CP(rd_bn_fwd_t, 12), I(13), st);
-    case RD_OP_POOL_BWD:
-        NARGS(17);
-        return rd_pool_bwd(P(0), P(1), CP(float, 2), CP(float, 3), F(4), I(5), P(6), I(7), (double*)P(8), I(9), I(10), I(11), I(12), I(13), CP(int32_t, 14), I(15), I(16), st);
-    case RD_OP_BN_APPLY:
-        NARGS(14);
-        return rd_bn_apply(P(0), P(1), P(2), CP(float, 3), CP(float, 4), CP(float, 5), F(6), I(7), I(8), I(9), I(10), I(11), CP(int32_t, 12), I(13), st);
-    case RD_OP_NCHW_TO_NHWC: NARGS(8); return rd_nchw_to_nhwc(CP(float, 0), P(1), I(2), I(3), I(4), I(5), I(6), I(7), st);
-    case RD_OP_NHWC_TO_NCHW:
-        NARGS(13);
-        return rd_nhwc_to_nchw(P(0), (float*)P(1), CP(float, 2), CP(float, 3), I(4), F(5), I(6), I(7), I(8), I(9), I(10), CP(int32_t, 11), I(12), st);
-    case RD_OP_GRAD_IN:
-        NARGS(16);
-        return rd_grad_in(CP(float, 0), P(1), P(2), CP(float, 3), CP(float, 4), (double*)P(5), I(6), F(7), I(8), I(9), I(10), I(11), I(12), I(13), CP(int32_t, 14), I(15), st);
-    case RD_OP_COLSUM: NARGS(8); return rd_colsum(P(0), (float*)P(1), (float*)P(2), L64(3), I(4), I(5), F(6), I(7), st);
-    case RD_OP_SEG_LOSS: NARGS(2); return rd_seg_loss(CP(rd_seg_loss_t, 0), I(1), st);
-    case RD_OP_REC_LOSS:
-        NARGS(15);
-        return rd_rec_loss(P(0), P(1), P(2), (float*)P(3), (float*)P(4), I(5), I(6), I(7), I(8), I(9), I(10), I(11), CP(int32_t, 12), F(13), I(14), st);
-    case RD_OP_ADAM_STEP: NARGS(1); return rd_adam_step(CP(rd_adam_t, 0), st);
-    case RD_OP_ZERO: NARGS(3); return rd_zero((void* const*)P(0), CP(int64_t, 1), I(2), st);
-    case RD_OP_RAM_MIX: NARGS(2); return rd_ram_mix(CP(rd_ram_t, 0), I(1), st);
-    default: return -1;
-    }
+    const OpRow* r = row_of(o);
+    return r ? r->call(o.a, st) : -1;
 }
 
 }  // namespace
@@ -287,9 +265,10 @@ int drain(Worker* w) {
     return w->err.exchange(0);
 }
 
-// Does an entry that makes a lane wait for the main stream follow main-lane launch i before the main stream is given anything else?
-// Then launch i carries the event of that fork on its own dispatch packet (common.h rd_launch) and the fork needs no record.
-bool fork_follows(const rd_launch_t* ops, int n, int i) {
+// ------------------------------------------------------------------------------------------------ the walk
+// Does an entry that makes a lane wait for the main stream follow entry i before the main stream is given anything else?  Then a launch
+// on the main stream at i can carry the event of that fork on its own dispatch packet (common.h rd_launch) and the fork needs no record.
+bool lane_edge_follows(const rd_launch_t* ops, int n, int i) {
     for (int j = i + 1; j < n; ++j) {
         const rd_launch_t& q = ops[j];
         if (q.op == RD_OP_FORK) {
@@ -301,101 +280,156 @@ bool fork_follows(const rd_launch_t* ops, int n, int i) {
     }
     return false;
 }
-// main-lane launch with the fork's event bound to its (last) kernel; *bound = the event if a launch took it, else null
-int call_with_stop_event(const rd_launch_t& o, void* st, hipEvent_t e, hipEvent_t* bound) {
-    rd_tls_stop_event = e;
-    rd_tls_stop_used = 0;
-    const int rc = call(o, st);
-    rd_tls_stop_event = nullptr;
-    *bound = rd_tls_stop_used ? e : nullptr;
+
+// THE interpretation of a list (include/ramdsir.h): entries in order, malformed ones refused, the open-lane mask carried in and out;
+// FORK / JOIN of lane 0 are ignored, a wait_main entry forks its lane first, a JOIN of a lane that is not open does nothing.  What a
+// step DOES is the executor's: x.fork(lane) makes streams[lane] wait for the main stream's current position, x.join(lane) makes the
+// main stream wait for streams[lane], x.launch(i, follows) launches entry i on its stream (follows(): lane_edge_follows, if asked).
+template <class X> int walk(const rd_launch_t* ops, int n, int n_streams, uint32_t* open_lanes, int* bad_index, X& x) {
+    uint32_t open = open_lanes ? *open_lanes : 0u;
+    int rc = 0, i = 0;
+    for (; i < n; ++i) {
+        const rd_launch_t& o = ops[i];
+        if (o.lane < 0 || o.lane >= n_streams || o.nargs < 0 || o.nargs > RD_LAUNCH_MAX_ARGS) { rc = -1; break; }
+        const uint32_t bit = 1u << o.lane;
+        if (o.op == RD_OP_FORK || o.op == RD_OP_JOIN) {
+            if (o.lane == 0 || (o.op == RD_OP_JOIN && !(open & bit))) continue;
+            open = o.op == RD_OP_FORK ? open | bit : open & ~bit;
+            rc = o.op == RD_OP_FORK ? x.fork(o.lane) : x.join(o.lane);
+        } else {
+            if (o.lane > 0 && o.wait_main) { open |= bit; rc = x.fork(o.lane); }
+            if (!rc) rc = x.launch(i, [&] { return lane_edge_follows(ops, n, i); });
+        }
+        if (rc) break;
+    }
+    if (rc && bad_index) *bad_index = i;
+    if (open_lanes) *open_lanes = open;
     return rc;
 }
 
-int run_list_threaded(const rd_launch_t* ops, int n, void* const* streams, int n_streams, uint32_t* open_lanes, int* bad_index) {
-    uint32_t open = open_lanes ? *open_lanes : 0u;
-    hipStream_t main_s = (hipStream_t)streams[0];
-    int dev = 0;
-    RD_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= EV_MAX_DEV) return -1;
+// ---- executor 1: everything from the calling thread.  at_main: an event bound to the LAST launch of the main stream (its dispatch
+// packet's completion), valid until the main stream is given anything else: forks at this position wait for it instead of recording
+// one.  `bind` is off under stream capture (a captured graph takes its edges from recorded events) and with one stream.
+struct Direct {
+    const rd_launch_t* ops;
+    void* const* streams;
+    hipStream_t main_s;
+    bool bind;
+    hipEvent_t at_main = nullptr;
+    int fork(int lane) {
+        hipStream_t to = (hipStream_t)streams[lane];
+        if (to == main_s) return 0;
+        (at_main ? g_forks_bound : g_forks_recorded).fetch_add(1, std::memory_order_relaxed);
+        return at_main ? (int)hipStreamWaitEvent(to, at_main, 0) : edge(main_s, to);
+    }
+    int join(int lane) {
+        if ((hipStream_t)streams[lane] != main_s) at_main = nullptr;    // the main stream now also waits for the lane
+        return edge((hipStream_t)streams[lane], main_s);
+    }
+    template <class F> int launch(int i, F follows) {
+        void* st = streams[ops[i].lane];
+        if ((hipStream_t)st != main_s) return call(ops[i], st);
+        at_main = nullptr;
+        hipEvent_t e;
+        if (!(bind && follows() && next_event(&e) == 0)) return call(ops[i], st);
+        rd_tls_stop_event = e;                                           // to the launch's (last) kernel: common.h rd_launch
+        rd_tls_stop_used = 0;
+        const int rc = call(ops[i], st);
+        rd_tls_stop_event = nullptr;
+        if (rd_tls_stop_used) at_main = e;                               // (rd_zero's fallback to the runtime's fills launches no kernel: the fork records)
+        return rc;
+    }
+};
+
+// ---- executor 2: feeds the lane worker threads (above); lane 0's entries are launched by the caller.  A worker's error surfaces at
+// the lane's join, or in finish() with bad_index -1.
+struct Threaded {
+    const rd_launch_t* ops;
+    void* const* streams;
+    hipStream_t main_s;
+    int dev;
     Worker* ws[32] = {};
-    int rc = 0, i = 0;
-    auto lane_worker = [&](int lane) -> Worker* {
+    int main_launch_rc = 0;
+    Worker* lane_worker(int lane) {
         if (!ws[lane]) {
             ws[lane] = worker_for(dev, lane);
             Cmd c{3, dev, nullptr, ops, (hipStream_t)streams[lane]};
             if (push(ws[lane], c)) return nullptr;
         }
         return ws[lane];
-    };
-    auto edge_to_lane = [&](int lane) -> int {                     // streams[lane] waits for the main stream's current position
+    }
+    int fork(int lane) {
         Worker* w = lane_worker(lane);
         if (!w) return -2;
         if ((hipStream_t)streams[lane] == main_s) return 0;
         hipEvent_t e;
-        const int err = worker_event(w, &e);
-        if (err) return err;
+        if (const int err = worker_event(w, &e)) return err;
         RD_CHECK(hipEventRecord(e, main_s));
         return push(w, Cmd{1, 0, e, nullptr, nullptr});
-    };
-    for (; i < n && rc == 0; ++i) {
-        const rd_launch_t& o = ops[i];
-        if (o.lane < 0 || o.lane >= n_streams || o.nargs < 0 || o.nargs > RD_LAUNCH_MAX_ARGS) { rc = -1; break; }
-        if (o.op == RD_OP_FORK) {
-            if (o.lane > 0) { rc = edge_to_lane(o.lane); open |= 1u << o.lane; }
-            continue;
-        }
-        if (o.op == RD_OP_JOIN) {
-            if (o.lane > 0 && (open & (1u << o.lane))) {
-                open &= ~(1u << o.lane);
-                Worker* w = lane_worker(o.lane);
-                if (!w) { rc = -2; break; }
-                if ((hipStream_t)streams[o.lane] != main_s) {
-                    hipEvent_t e;
-                    rc = worker_event(w, &e);
-                    if (rc) break;
-                    rc = push(w, Cmd{2, 0, e, nullptr, nullptr});
-                    if (rc) break;
-                    rc = drain(w);                                 // the record has been enqueued (and everything before it)
-                    if (rc) break;
-                    rc = (int)hipStreamWaitEvent(main_s, e, 0);
-                } else {
-                    rc = drain(w);
-                }
-            }
-            continue;
-        }
-        if (o.lane == 0) {
-            rc = call(o, (void*)main_s);
-            continue;
-        }
-        if (o.wait_main) {
-            rc = edge_to_lane(o.lane);
-            open |= 1u << o.lane;
-            if (rc) break;
-        }
-        Worker* w = lane_worker(o.lane);
-        if (!w) { rc = -2; break; }
-        rc = push(w, Cmd{0, i, nullptr, nullptr, nullptr});
     }
-    if (rc && bad_index) *bad_index = i;
-    for (int k = 1; k < n_streams; ++k)
-        if (ws[k]) {
-            const int e = drain(ws[k]);
-            if (e && !rc) { rc = e; if (bad_index) *bad_index = -1; }
-        }
-    if (open_lanes) *open_lanes = open;
-    return rc;
-}
+    int join(int lane) {
+        Worker* w = lane_worker(lane);
+        if (!w) return -2;
+        if ((hipStream_t)streams[lane] == main_s) return drain(w);
+        hipEvent_t e;
+        int rc = worker_event(w, &e);
+        if (!rc) rc = push(w, Cmd{2, 0, e, nullptr, nullptr});
+        if (!rc) rc = drain(w);                                    // the record has been enqueued (and everything before it)
+        return rc ? rc : (int)hipStreamWaitEvent(main_s, e, 0);
+    }
+    template <class F> int launch(int i, F) {
+        if (ops[i].lane == 0) return main_launch_rc = call(ops[i], (void*)main_s);
+        Worker* w = lane_worker(ops[i].lane);
+        return w ? push(w, Cmd{0, i, nullptr, nullptr, nullptr}) : -2;
+    }
+    // every worker has enqueued what it was given (descriptors may be changed by the caller afterwards)
+    int finish(int rc, int n_streams, int* bad_index) {
+        if (main_launch_rc && bad_index) ++*bad_index;             // (this walk has always named the entry BEHIND a failing main-lane launch)
+        for (int k = 1; k < n_streams; ++k)
+            if (ws[k]) {
+                const int e = drain(ws[k]);
+                if (e && !rc) { rc = e; if (bad_index) *bad_index = -1; }
+            }
+        return rc;
+    }
+};
+
+// ---- executor 3: launches nothing and writes the steps out (rd_run_list_schedule).  Lanes are taken as distinct streams.
+struct Recorder {
+    const rd_launch_t* ops;
+    rd_step_t* steps;
+    int n = 0;
+    int add(int kind, int lane, int index, int carries) { steps[n++] = rd_step_t{kind, lane, index, carries}; return 0; }
+    int fork(int lane) { return add(RD_STEP_FORK, lane, -1, 0); }
+    int join(int lane) { return add(RD_STEP_JOIN, lane, -1, 0); }
+    template <class F> int launch(int i, F follows) { return row_of(ops[i]) ? add(RD_STEP_LAUNCH, ops[i].lane, i, ops[i].lane == 0 && follows()) : -1; }
+};
 
 }  // namespace
 
-// which main-lane entries of a list would carry a fork's event on their own dispatch packet (host logic only: no stream, no launch)
+extern "C" int rd_op_code(const char* entry_point) {
+    for (int k = 0; entry_point && k < RD_OP_END_ - RD_OP_CONV; ++k)
+        if (!strcmp(entry_point, OPS[k].name)) return RD_OP_CONV + k;
+    return -1;
+}
+
+extern "C" int rd_run_list_schedule(const rd_launch_t* ops, int n, int n_streams, uint32_t* open_lanes, int* bad_index, rd_step_t* steps, int* n_steps) {
+    if (n_streams < 1 || n_streams > 32 || n < 0 || !n_steps || (n > 0 && (!ops || !steps))) return -1;
+    Recorder x{ops, steps};
+    const int rc = walk(ops, n, n_streams, open_lanes, bad_index, x);
+    *n_steps = x.n;
+    return rc;
+}
+
+// which main-lane entries of a list would carry a fork's event on their own dispatch packet: the schedule's `carries`, by entry
 extern "C" int rd_run_list_fork_plan(const rd_launch_t* ops, int n, unsigned char* carries) {
     if (n < 0 || (n > 0 && (!ops || !carries))) return -1;
-    for (int i = 0; i < n; ++i) {
-        const rd_launch_t& o = ops[i];
-        carries[i] = (o.op != RD_OP_FORK && o.op != RD_OP_JOIN && o.lane == 0 && fork_follows(ops, n, i)) ? 1 : 0;
-    }
+    memset(carries, 0, (size_t)n);
+    std::vector<rd_step_t> steps(2 * (size_t)n);
+    int n_steps = 0;
+    (void)rd_run_list_schedule(ops, n, 32, nullptr, nullptr, steps.data(), &n_steps);
+    for (int k = 0; k < n_steps; ++k)
+        if (steps[k].kind == RD_STEP_LAUNCH) carries[steps[k].index] = (unsigned char)steps[k].carries;
     return 0;
 }
 
@@ -404,15 +438,9 @@ extern "C" void rd_run_list_fork_counts(long long* bound, long long* recorded) {
     if (recorded) *recorded = g_forks_recorded.load();
 }
 
-extern "C" int rd_run_list_bind_fork_events(int enable) {
-    const int old = g_bind_fork_events.exchange(enable ? 1 : 0);
-    return old;
-}
+extern "C" int rd_run_list_bind_fork_events(int enable) { return g_bind_fork_events.exchange(enable ? 1 : 0); }
 
-extern "C" int rd_run_list_threads(int enable) {
-    const int old = g_threads_enabled.exchange(enable ? 1 : 0);
-    return old;
-}
+extern "C" int rd_run_list_threads(int enable) { return g_threads_enabled.exchange(enable ? 1 : 0); }
 
 extern "C" int rd_join_lanes(void* const* streams, int n_streams, uint32_t mask) {
     for (int k = 1; k < n_streams && k < 32; ++k)
@@ -426,62 +454,17 @@ extern "C" int rd_join_lanes(void* const* streams, int n_streams, uint32_t mask)
 extern "C" int rd_run_list(const rd_launch_t* ops, int n, void* const* streams, int n_streams, uint32_t* open_lanes, int* bad_index) {
     if (n_streams < 1 || n_streams > 32) return -1;
     hipStream_t main_s = (hipStream_t)streams[0];
-    if (n_streams > 1 && g_threads_enabled.load()) {
-        // worker threads only outside stream capture (a capture is recorded by the capturing thread)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(main_s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone)
-            return run_list_threaded(ops, n, streams, n_streams, open_lanes, bad_index);
-    }
-    uint32_t open = open_lanes ? *open_lanes : 0u;
-    int rc = 0, i = 0;
-    // at_main: an event bound to the LAST launch of the main stream (its dispatch packet's completion), valid until the main stream is
-    // given anything else: forks at this position wait for it instead of recording one.  Not under stream capture (a captured graph
-    // takes its edges from recorded events).
-    hipEvent_t at_main = nullptr;
+    // worker threads and bound fork events only with side streams and outside stream capture (a capture is recorded by the capturing
+    // thread, from recorded events)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool bind = n_streams > 1 && g_bind_fork_events.load() && hipStreamIsCapturing(main_s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
-    auto fork_edge = [&](hipStream_t to) -> int {
-        if (to == main_s) return 0;
-        if (at_main) {
-            g_forks_bound.fetch_add(1, std::memory_order_relaxed);
-            return (int)hipStreamWaitEvent(to, at_main, 0);
-        }
-        g_forks_recorded.fetch_add(1, std::memory_order_relaxed);
-        return edge(main_s, to);
-    };
-    for (; i < n && rc == 0; ++i) {
-        const rd_launch_t& o = ops[i];
-        if (o.lane < 0 || o.lane >= n_streams || o.nargs < 0 || o.nargs > RD_LAUNCH_MAX_ARGS) { rc = -1; break; }
-        hipStream_t st = (hipStream_t)streams[o.lane];
-        if (o.op == RD_OP_FORK) {
-            if (o.lane > 0) { rc = fork_edge(st); open |= 1u << o.lane; }
-            continue;
-        }
-        if (o.op == RD_OP_JOIN) {
-            if (o.lane > 0 && (open & (1u << o.lane))) {
-                rc = edge(st, main_s);
-                open &= ~(1u << o.lane);
-                if (st != main_s) at_main = nullptr;              // the main stream now also waits for the lane
-            }
-            continue;
-        }
-        if (o.lane > 0 && o.wait_main) {
-            rc = fork_edge(st);
-            open |= 1u << o.lane;
-            if (rc) break;
-        }
-        if (st == main_s) {
-            at_main = nullptr;
-            hipEvent_t e;
-            if (bind && fork_follows(ops, n, i) && next_event(&e) == 0) rc = call_with_stop_event(o, (void*)st, e, &at_main);   // (an entry that
-            // launched no kernel -- rd_zero's fallback to the runtime's fills -- leaves at_main null: the fork records)
-            else rc = call(o, (void*)st);
-        } else {
-            rc = call(o, (void*)st);
-        }
-        if (rc) break;
+    const bool eager = n_streams > 1 && hipStreamIsCapturing(main_s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
+    if (eager && g_threads_enabled.load()) {
+        int dev = 0;
+        RD_CHECK(hipGetDevice(&dev));
+        if (dev < 0 || dev >= EV_MAX_DEV) return -1;
+        Threaded x{ops, streams, main_s, dev};
+        return x.finish(walk(ops, n, n_streams, open_lanes, bad_index, x), n_streams, bad_index);
     }
-    if (rc && bad_index) *bad_index = i;
-    if (open_lanes) *open_lanes = open;
-    return rc;
+    Direct x{ops, streams, main_s, eager && g_bind_fork_events.load() != 0};
+    return walk(ops, n, n_streams, open_lanes, bad_index, x);
 }

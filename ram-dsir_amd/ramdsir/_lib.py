@@ -1,6 +1,7 @@
 """ctypes binding of libramdsir_hip.so (include/ramdsir.h).  No fallback: if the HIP library is
 missing or a call fails, this raises -- the product path never routes around the kernels."""
 import ctypes as C
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -138,14 +139,23 @@ class RdLaunch(C.Structure):
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
 
 
-# RD_OP_* (include/ramdsir.h) by entry-point name
-OP_FORK, OP_JOIN = 1, 2
-OP_CODES = {name: 10 + i for i, name in enumerate((
-    'rd_conv', 'rd_wgrad', 'rd_conv_bwd_fused', 'rd_conv_bwd_fused_reduce', 'rd_pack_weights_batched',
-    'rd_bn_finalize_fwd', 'rd_bn_finalize_bwd', 'rd_gn_finalize_fwd', 'rd_gn_finalize_bwd',
-    'rd_up_stats', 'rd_bn_stats', 'rd_up_bwd', 'rd_pool_fwd', 'rd_pool_bwd', 'rd_bn_apply',
-    'rd_nchw_to_nhwc', 'rd_nhwc_to_nchw', 'rd_grad_in', 'rd_colsum',
-    'rd_seg_loss', 'rd_rec_loss', 'rd_adam_step', 'rd_zero', 'rd_ram_mix'))}
+class RdStep(C.Structure):
+    """rd_step_t (include/ramdsir.h): one step of rd_run_list_schedule."""
+    _fields_ = [('kind', i32), ('lane', i32), ('index', i32), ('carries', i32)]
+
+
+OP_FORK, OP_JOIN = 1, 2                              # RD_OP_FORK, RD_OP_JOIN
+STEP_LAUNCH, STEP_FORK, STEP_JOIN = range(3)         # RD_STEP_*
+
+
+@functools.lru_cache(maxsize=None)
+def op_code(name):
+    """The RD_OP_* code of an entry point, from the library's own table (include/ramdsir.h RD_LAUNCH_OPS)."""
+    code = lib().rd_op_code(name.encode())
+    if code < 0:
+        raise KeyError('%s cannot go into a launch list' % name)
+    return code
+
 
 _SIGS = {
     'rd_ram_workspace': (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -200,6 +210,9 @@ _SIGS = {
     'rd_run_list_bind_fork_events': (C.c_int, [C.c_int]),
     'rd_run_list_fork_counts': (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     'rd_run_list_fork_plan': (C.c_int, [C.POINTER(RdLaunch), C.c_int, C.POINTER(C.c_ubyte)]),
+    'rd_run_list_schedule': (C.c_int, [C.POINTER(RdLaunch), C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(RdStep),
+                                       C.POINTER(C.c_int)]),
+    'rd_op_code': (C.c_int, [C.c_char_p]),
     'rd_tb_grids_workspace': (i64, [C.c_int]),
     'rd_tb_grids': (C.c_int, [C.POINTER(RdTbGrid), C.c_int, vp, i64, vp]),
     'rd_crc32c': (C.c_uint32, [vp, C.c_size_t, C.c_uint32]),

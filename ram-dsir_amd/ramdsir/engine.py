@@ -881,7 +881,7 @@ class Plan:
         esz = 2 if self.dtype == torch.bfloat16 else 4
         nb = 2 if ((Cout + 31) // 32 * 32) % 64 == 0 else 1
         if nb == 2 and self.dtype == torch.bfloat16:
-            # csrc/conv_big.hip rd_conv_big_dispatch: grids below RD_CONV_NB1_BELOW 64-wide workgroups run 32-wide tiles
+            # csrc/conv_big.hip rd_conv_nb2: grids below RD_CONV_NB1_BELOW 64-wide workgroups run 32-wide tiles
             wgs64 = ((W + 31) // 32) * ((H + 7) // 8) * N * (((Cout + 31) // 32 * 32) // 64)
             if wgs64 < T.options()['conv_nb1_below']:
                 nb = 1
@@ -928,58 +928,51 @@ class Plan:
         and sync_op('fork'|'join', lane) entries order a lane against the main stream.  A lane missing from
         `lanes` falls back to the main stream (the list order is a valid sequential schedule).  Works eagerly and
         under hipGraph capture (fork/join through events).  Returns the set of lanes that still have to be joined.
-        wrap(op, stream, launch) may time a launch: it must call launch() exactly once."""
-        open_lanes = set()
-        for op in ops:
-            fn, args = op[0], op[1]
-            meta = op[2] if len(op) > 2 else None
-            if fn is None:
-                kind, lane = args
-                st = lanes.get(lane)
-                if st is None:
-                    continue
-                if kind == 'fork':
-                    st.wait_stream(main)
-                    open_lanes.add(lane)
-                elif lane in open_lanes:
-                    main.wait_stream(st)
-                    open_lanes.discard(lane)
-                continue
-            st = main
-            if meta is not None:
-                if meta.get('lane') == 'rec' and 'rec' in lanes:
-                    st = lanes['rec']
-                elif meta.get('side') and 'side0' in lanes:
-                    name = 'side%d' % meta.get('side_idx', 0)
-                    if name not in lanes:
-                        name = 'side0'
-                    st = lanes[name]
-                    st.wait_stream(main)
-                    open_lanes.add(name)
-
-            def launch(fn=fn, args=args, st=st):
-                err = fn(*args, st.cuda_stream)
-                if err:
-                    raise RuntimeError('ramdsir HIP launch failed: %s -> %d' % (fn.__name__, err))
-            if wrap is None:
-                launch()
+        wrap(op, stream, launch) may time a launch: it must call launch() exactly once.  The routing is LaunchList's and the order of
+        launches and stream waits is rd_run_list's own walk (rd_run_list_schedule): this loop only executes its steps.  Like a native
+        list, the ops are compiled once (per ops and lanes: _compiled) -- a meta edited afterwards is not seen."""
+        key = (tuple(map(id, ops)), tuple(lanes))
+        ll = Plan._compiled.get(key)
+        if ll is None:
+            if len(Plan._compiled) >= 32:
+                Plan._compiled.clear()
+            ll = Plan._compiled[key] = LaunchList(tuple(ops), tuple(lanes), pack=False)     # (it keeps the ops alive: their ids stay theirs)
+        steps, mask = ll.schedule()
+        streams = [main] + [lanes[nm] for nm in ll.lane_names]
+        for kind, lane, k in steps:
+            st = streams[lane]
+            if kind == L.STEP_FORK:
+                st.wait_stream(main)
+            elif kind == L.STEP_JOIN:
+                main.wait_stream(st)
             else:
-                wrap(op, st, launch)
-        return open_lanes
+                op = ll.ops[k]
+
+                def launch(fn=op[0], args=op[1], st=st):
+                    err = fn(*args, st.cuda_stream)
+                    if err:
+                        raise RuntimeError('ramdsir HIP launch failed: %s -> %d' % (fn.__name__, err))
+                if wrap is None:
+                    launch()
+                else:
+                    wrap(op, st, launch)
+        return {nm for k, nm in enumerate(ll.lane_names) if mask >> (k + 1) & 1}
+
+    _compiled = {}
 
 
 class LaunchList:
-    """A launch list compiled for rd_run_list (include/ramdsir.h): the same entries, lanes and fork / join semantics as
-    Plan.run_lanes, walked in C++ with ONE ctypes call per segment instead of one call + one event record / stream wait per entry
-    (2.2 ms of host time per step -> a fraction).  `lane_names`: the lanes that exist, in stream-index order (index 0 is the main
-    stream); entries of a lane that does not exist run on the main stream, exactly as in run_lanes.  The descriptors referenced by
-    the entries are owned by the plans (Plan.keep); `ops` is kept so that they stay alive with the list."""
+    """A launch list compiled for rd_run_list (include/ramdsir.h): THE place that turns (fn, args[, meta]) into an entry -- op code,
+    lane, wait_main (as Plan.run_lanes says), packed arguments -- walked in C++ with ONE ctypes call per segment instead of one call +
+    one event record / stream wait per entry (2.2 ms of host time per step -> a fraction).  `lane_names`: the lanes that exist, in
+    stream-index order (index 0 is the main stream).  op_index[i]: which of `ops` entry i came from.  The descriptors the entries
+    reference are owned by the plans (Plan.keep); `ops` is kept so that they stay alive with the list.  pack=False: no arguments."""
 
-    def __init__(self, ops, lane_names):
+    def __init__(self, ops, lane_names, pack=True):
         self.lane_names = list(lane_names)
         idx = {name: i + 1 for i, name in enumerate(self.lane_names)}
-        entries = []
-        for op in ops:
+        entries, self.op_index = [], []
+        for k, op in enumerate(ops):
             fn, args = op[0], op[1]
             meta = op[2] if len(op) > 2 else None
             e = L.RdLaunch()
@@ -988,39 +981,53 @@ class LaunchList:
                 if lane not in idx:
                     continue
                 e.op, e.lane = (L.OP_FORK if kind == 'fork' else L.OP_JOIN), idx[lane]
-                entries.append(e)
-                continue
-            e.op = L.OP_CODES[fn.__name__]
-            if meta is not None:
-                if meta.get('lane') == 'rec' and 'rec' in idx:
-                    e.lane = idx['rec']
-                elif meta.get('side') and 'side0' in idx:
-                    name = 'side%d' % meta.get('side_idx', 0)
-                    e.lane, e.wait_main = idx[name if name in idx else 'side0'], 1
-            types = fn.argtypes[:-1]                         # without the trailing stream
-            assert len(types) == len(args) <= 18, (fn.__name__, len(types), len(args))
-            e.nargs = len(args)
-            for i, (v, t) in enumerate(zip(args, types)):
-                e.a[i] = L.pack_arg(v, t)
+            else:
+                e.op = L.op_code(fn.__name__)
+                if meta is not None:
+                    if meta.get('lane') == 'rec' and 'rec' in idx:
+                        e.lane = idx['rec']
+                    elif meta.get('side') and 'side0' in idx:
+                        name = 'side%d' % meta.get('side_idx', 0)
+                        e.lane, e.wait_main = idx[name if name in idx else 'side0'], 1
+                e.nargs = len(args)
+                if pack:
+                    types = fn.argtypes[:-1]                     # without the trailing stream
+                    assert len(types) == len(args) <= 18, (fn.__name__, len(types), len(args))
+                    for i, (v, t) in enumerate(zip(args, types)):
+                        e.a[i] = L.pack_arg(v, t)
             entries.append(e)
+            self.op_index.append(k)
         self.n = len(entries)
         self.arr = (L.RdLaunch * max(self.n, 1))(*entries)
         self.ops = ops
-        self._bad = C.c_int(-1)
+        self._bad, self._schedule = C.c_int(-1), None
+
+    def _check(self, err):
+        bad = self._bad.value
+        if err:
+            raise RuntimeError('ramdsir launch list failed at entry %d (op %d): error %d' % (bad, self.arr[bad].op if 0 <= bad < self.n else -1, err))
+
+    def _streams(self, main, lanes):
+        return (L.vp * (1 + len(self.lane_names)))(main.cuda_stream, *[lanes[nm].cuda_stream for nm in self.lane_names])
+
+    def schedule(self):
+        """rd_run_list_schedule, once: ([(RD_STEP_* kind, lane, index into `ops` of a launch or -1) in order], bitmask of lanes left open)"""
+        if self._schedule is None:
+            steps, n_steps, mask = (L.RdStep * max(2 * self.n, 1))(), C.c_int(0), C.c_uint32(0)
+            self._check(L.lib().rd_run_list_schedule(self.arr, self.n, 1 + len(self.lane_names), C.byref(mask), C.byref(self._bad), steps, C.byref(n_steps)))
+            self._schedule = ([(s.kind, s.lane, self.op_index[s.index] if s.index >= 0 else -1) for s in steps[:n_steps.value]], mask.value)
+        return self._schedule
 
     def run(self, main, lanes, open_mask=0):
         """Enqueue the list; returns the bitmask of lanes left open (bit k = lane_names[k - 1])."""
-        streams = (L.vp * (1 + len(self.lane_names)))(main.cuda_stream, *[lanes[nm].cuda_stream for nm in self.lane_names])
+        streams = self._streams(main, lanes)
         mask = C.c_uint32(open_mask)
-        err = L.lib().rd_run_list(self.arr, self.n, streams, len(streams), C.byref(mask), C.byref(self._bad))
-        if err:
-            bad = self._bad.value
-            raise RuntimeError('ramdsir launch list failed at entry %d (op %d): error %d' % (bad, self.arr[bad].op if 0 <= bad < self.n else -1, err))
+        self._check(L.lib().rd_run_list(self.arr, self.n, streams, len(streams), C.byref(mask), C.byref(self._bad)))
         return mask.value
 
     def join(self, main, lanes, mask):
         if mask:
-            streams = (L.vp * (1 + len(self.lane_names)))(main.cuda_stream, *[lanes[nm].cuda_stream for nm in self.lane_names])
+            streams = self._streams(main, lanes)
             L.check(L.lib().rd_join_lanes(streams, len(streams), mask), 'rd_join_lanes')
 
 

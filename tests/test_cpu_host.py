@@ -69,7 +69,7 @@ def test_launch_list_packing_and_lanes():
            (lib.rd_adam_step, (ctypes.byref(L.RdAdam()),))]
     ll = E.LaunchList(ops, ('side0', 'rec'))
     got = [(e.op, e.lane, e.wait_main, e.nargs) for e in ll.arr[:ll.n]]
-    oc = L.OP_CODES
+    oc = {n: L.op_code(n) for n in ('rd_conv', 'rd_pool_fwd', 'rd_wgrad', 'rd_adam_step')}
     assert got == [(oc['rd_conv'], 0, 0, 2), (L.OP_FORK, 2, 0, 0), (oc['rd_pool_fwd'], 2, 0, 14), (oc['rd_wgrad'], 1, 1, 2),
                    (L.OP_JOIN, 2, 0, 0), (oc['rd_adam_step'], 0, 0, 1)]
     e = ll.arr[2]
@@ -95,17 +95,23 @@ def test_launch_list_packing_and_lanes():
     c2 = (ctypes.c_ubyte * l2.n)()
     assert lib.rd_run_list_fork_plan(l2.arr, l2.n, c2) == 0
     assert list(c2) == [0, 1, 0, 0, 0, 0, 0, 0]
-    # the op codes of the binding are the header's enum
+    # the op codes of the binding are the library's table (include/ramdsir.h RD_LAUNCH_OPS): these 24 names with these values, which are ABI
+    names = ('rd_conv', 'rd_wgrad', 'rd_conv_bwd_fused', 'rd_conv_bwd_fused_reduce', 'rd_pack_weights_batched',
+             'rd_bn_finalize_fwd', 'rd_bn_finalize_bwd', 'rd_gn_finalize_fwd', 'rd_gn_finalize_bwd',
+             'rd_up_stats', 'rd_bn_stats', 'rd_up_bwd', 'rd_pool_fwd', 'rd_pool_bwd', 'rd_bn_apply',
+             'rd_nchw_to_nhwc', 'rd_nhwc_to_nchw', 'rd_grad_in', 'rd_colsum',
+             'rd_seg_loss', 'rd_rec_loss', 'rd_adam_step', 'rd_zero', 'rd_ram_mix')
+    values = (10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33)
+    assert [lib.rd_op_code(n.encode()) for n in names] == list(values) == [L.op_code(n) for n in names]
+    for other in ('rd_wgrad_reduce', 'rd_run_list', 'rd_conv_route', 'rd_con', 'rd_convx', ''):
+        assert lib.rd_op_code(other.encode()) == -1
+    assert lib.rd_op_code(None) == -1 and (L.OP_FORK, L.OP_JOIN) == (1, 2)
+    with pytest.raises(KeyError):
+        L.op_code('rd_wgrad_reduce')
     txt = open(os.path.join(ROOT, 'include', 'ramdsir.h')).read()
-    enum = re.search(r'enum \{\s*RD_OP_FORK = 1, RD_OP_JOIN = 2,(.*?)\};', txt, re.S).group(1)
-    names, val = [], 10
-    for tok in [t.strip() for t in enum.replace('\n', ' ').split(',') if t.strip()]:
-        if '=' in tok:
-            tok, v = [x.strip() for x in tok.split('=')]
-            val = int(v)
-        names.append((tok, val))
-        val += 1
-    assert {('RD_OP_' + k[3:].upper(), v) for k, v in oc.items()} == set(names)
+    table = re.search(r'#define RD_LAUNCH_OPS\(X\)(.*?)\n#define', txt, re.S).group(1)
+    assert tuple(re.findall(r'X\(\w+, (\w+)\)', table)) == names            # the header's rows, in this order
+    assert [s.upper() for s in re.findall(r'X\((\w+), rd_', table)] == [n[3:].upper() for n in names]
 
 
 def test_parameter_layout_equals_reference_manifest(golden_dir):
