@@ -655,6 +655,42 @@ int64_t rd_vol_post_workspace(const rd_val_volume_t* volumes_host, int B);
 int rd_vol_post(const uint8_t* pred, uint8_t* post, int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int32_t* counts, int n_slots,
                 void* workspace, int64_t workspace_bytes, const rd_val_volume_t* volumes_host, int B, void* stream);
 
+/* The fused validation forward (train.py --fused_val, ramdsir/infer.py EvalForward), csrc/infer.hip: what a forward-only launch list
+ * with frozen BatchNorm (engine.Plan frozen_bn: rd_conv and rd_pool_fwd entries only) needs around it.  The network input and the
+ * logits are NHWC in the storage dtype (RD_F32 / RD_BF16) with a channel stride `cstride` in elements; a stored value is widened to
+ * fp32 exactly.  All four launch on `stream`, never wait for work on any stream, and return -1 for an invalid argument or record
+ * before anything is launched.  No reference counterpart beyond the lines the NCHW forms above cite.
+ *   rd_bn_eval_coeffs      scale / shift of ALL n_sites BatchNorm sites in one launch, from the running statistics: the eval branch of
+ *                          rd_bn_finalize_fwd (invstd = 1 / sqrt(running_var + eps), scale = gamma * invstd,
+ *                          shift = beta - running_mean * scale; the same device function, so the same bits).  sites_dev: a DEVICE
+ *                          table, written once when the plan is built and complete in memory before the call; max_C: the largest C
+ *                          in it.  The call reads the table back through a stream of its own to check it (the host waits for that
+ *                          copy of n_sites records, not for `stream`): a null pointer or C < 1 or C > max_C in a site returns -1.
+ *   rd_val_threshold_nhwc  rd_val_threshold on logits [B][Sh][Sw][cstride], channel 0 the cup and 1 the disc (cstride >= 2): the same
+ *                          operation sequence on the widened values, records, return codes and chunking.
+ *   rd_vol_stack_nhwc      rd_vol_stack straight into the plan's input: out[b][y][x][c] = slice frames[b] - 1 + c for c < 3 (fp32 ->
+ *                          storage dtype rounded to nearest even, what rd_nchw_to_nhwc does to rd_vol_stack's output), zeros in
+ *                          channels 3 .. cstride - 1 (cstride >= 3) and in every channel of an empty slot.
+ *   rd_vol_argmax_nhwc     rd_vol_argmax on logits [B][H][W][cstride] (cstride >= 2): 1 iff l1 > l0 on the widened values; gt_empty
+ *                          and empty slots as there. */
+typedef struct {
+    const float* gamma;
+    const float* beta;
+    const float* running_mean;
+    const float* running_var;
+    float* scale;               /* [C] */
+    float* shift;               /* [C] */
+    int32_t C;
+    int32_t pad_;
+} rd_bn_eval_site_t;
+int rd_bn_eval_coeffs(const rd_bn_eval_site_t* sites_dev, int n_sites, int max_C, float eps, void* stream);
+int rd_val_threshold_nhwc(const void* logits, int dtype, int cstride, int B, int Sh, int Sw, const rd_val_image_t* images_host,
+                          uint8_t* mask, int64_t mask_bytes, void* stream);
+int rd_vol_stack_nhwc(const float* volume, int D, int H, int W, const int32_t* frames_host, int B, void* out, int dtype, int cstride,
+                      void* stream);
+int rd_vol_argmax_nhwc(const void* logits, int dtype, int cstride, int B, int H, int W, const int32_t* frames_host,
+                       const uint8_t* gt_empty, int D, uint8_t* pred, void* stream);
+
 /* TensorBoard image summaries (train.py --tb_images, ramdsir/tb_images.py), csrc/tb_grid.hip: replaces the make_grid(...) +
  * writer.add_image(...) blocks of code/train.py:306-329 (Fundus) and :475-496 (Prostate) -- the slicing, sigmoid / tanh / argmax,
  * decode_seg_map_sequence (code/utils/utils.py:285-336), torchvision.utils.make_grid and tensorboardX's float -> uint8 conversion --

@@ -9,9 +9,14 @@
 // argmax's first maximum.  Integer atomics only; no workgroup waits for another: every phase is a launch of its own.
 #include "common.h"
 #include "val_uf.h"
+#include "val_common.h"
 #include "../../include/ramdsir.h"
 
 namespace {
+
+using rdval::kMaxPixels;
+using rdval::sigmoid_f;
+using rdval::valid_images;
 
 constexpr int kThreads = 256;
 constexpr int kPerThread = 4;                               // pixels per thread of the per-pixel kernels (strided by kThreads)
@@ -50,9 +55,7 @@ __device__ __forceinline__ Plane plane_of(const ValPlaneSet& c, int p) {
 // ---- stage a ------------------------------------------------------------------------------------------------------------------------
 // F.interpolate(sigmoid(logits), (H, W), mode='bilinear', align_corners=False) > 0.75, one thread per output pixel; the probability
 // map at native size is never stored.  Contraction is off in here: the source coordinate and the three lerps round after every
-// operation, as resize_threshold_model's float32 numpy does.
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-
+// operation, as resize_threshold_model's float32 numpy does.  (sigmoid_f: val_common.h, shared with the NHWC form in infer.hip.)
 __global__ __launch_bounds__(kThreads) void val_threshold_kernel(const float* __restrict__ logits, uint8_t* __restrict__ mask, ValPlaneSet c,
                                                                  int b0, int Sh, int Sw) {
 #pragma clang fp contract(off)
@@ -242,15 +245,6 @@ __global__ __launch_bounds__(kThreads) void val_fill_kernel(uint8_t* __restrict_
         for (int w = 0; w < kThreads / 64; ++w) v += part[w][threadIdx.x];
         if (v) atomicAdd(counts + pl.slot + threadIdx.x, v);
     }
-}
-
-constexpr int64_t kMaxPixels = 1 << 28;                    // per plane: node indices and areas stay far inside 31 bits
-
-bool valid_images(const rd_val_image_t* im, int B) {
-    if (!im || B < 0) return false;
-    for (int i = 0; i < B; ++i)
-        if (im[i].h < 1 || im[i].w < 1 || (int64_t)im[i].h * im[i].w > kMaxPixels || im[i].off < 0) return false;
-    return true;
 }
 
 int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }

@@ -10,16 +10,19 @@
 // every phase is a launch of its own.
 #include "common.h"
 #include "val_uf.h"
+#include "val_common.h"
 #include "../../include/ramdsir.h"
 
 namespace {
 
+using rdval::aligned;
+using rdval::frames_chunk;
+using rdval::kMaxVoxels;
+using rdval::valid_frames;
+using rdval::VolFrames;                                     // the frames of a chunk as they travel in the kernel arguments
+
 constexpr int kThreads = 256;
 constexpr int kPerThread = 4;                               // elements per thread of the per-element kernels (strided by kThreads)
-
-struct VolFrames {
-    int32_t jj[RD_VAL_CHUNK];                               // frame of each slot of the chunk, -1: empty
-};
 
 // ---- the 2.5-D batch ----------------------------------------------------------------------------------------------------------------
 // Slot b of the batch is the 3 * H * W consecutive floats of the volume that start at slice jj - 1.  T = uint4 (16 B per lane) when H * W
@@ -239,8 +242,6 @@ __global__ __launch_bounds__(kThreads) void vol_select_kernel(const uint8_t* __r
     }
 }
 
-constexpr int64_t kMaxVoxels = 1 << 28;                    // per volume: node indices and areas stay far inside 31 bits
-
 bool valid_volumes(const rd_val_volume_t* v, int B) {
     if (!v || B < 0) return false;
     for (int i = 0; i < B; ++i)
@@ -248,32 +249,12 @@ bool valid_volumes(const rd_val_volume_t* v, int B) {
     return true;
 }
 
-// every slot empty (-1) or a frame with both neighbours inside the volume; the frames increase, so no two slots write one slice
-bool valid_frames(const int32_t* f, int B, int D) {
-    if (!f || B < 1) return false;
-    int last = 0;
-    for (int i = 0; i < B; ++i) {
-        if (f[i] == -1) continue;
-        if (f[i] <= last || f[i] > D - 2) return false;
-        last = f[i];
-    }
-    return true;
-}
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
 
 int64_t total_nodes(const rd_val_volume_t* v, int B) {
     int64_t n = 0;
     for (int i = 0; i < B; ++i) n += (int64_t)v[i].d * v[i].h * v[i].w;
     return n;
-}
-
-VolFrames frames_chunk(const int32_t* f, int b0, int n) {
-    VolFrames c;
-    for (int i = 0; i < RD_VAL_CHUNK; ++i) c.jj[i] = i < n ? f[b0 + i] : -1;
-    return c;
 }
 
 }  // namespace

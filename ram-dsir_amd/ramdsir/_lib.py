@@ -123,7 +123,12 @@ class RdValVolume(C.Structure):
     _fields_ = [('off', i64), ('gt_off', i64), ('d', i32), ('h', i32), ('w', i32), ('slot', i32)]
 
 
-TB_F32, TB_BF16, TB_I64 = range(3)                                   # RD_TB_* element types
+class RdBnEvalSite(C.Structure):
+    """rd_bn_eval_site_t (include/ramdsir.h): one BatchNorm site of a frozen plan, a row of rd_bn_eval_coeffs' device table."""
+    _fields_ = [('gamma', fp), ('beta', fp), ('running_mean', fp), ('running_var', fp), ('scale', fp), ('shift', fp), ('C', i32), ('pad_', i32)]
+
+
+TB_F32, TB_BF16, TB_I64 = range(3)                                  # RD_TB_* element types
 TB_IDENTITY, TB_SIGMOID, TB_TANH, TB_ARGMAX, TB_LABEL = range(5)      # RD_TB_* transforms
 TB_MAX_GRIDS, TB_PALETTE = 8, 21
 
@@ -226,6 +231,10 @@ _SIGS = {
     'rd_vol_argmax': (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.POINTER(i32), vp, C.c_int, vp, vp]),
     'rd_vol_post_workspace': (i64, [C.POINTER(RdValVolume), C.c_int]),
     'rd_vol_post': (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, vp, i64, C.POINTER(RdValVolume), C.c_int, vp]),
+    'rd_bn_eval_coeffs': (C.c_int, [vp, C.c_int, C.c_int, f32, vp]),
+    'rd_val_threshold_nhwc': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RdValImage), vp, i64, vp]),
+    'rd_vol_stack_nhwc': (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.POINTER(i32), C.c_int, vp, C.c_int, C.c_int, vp]),
+    'rd_vol_argmax_nhwc': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(i32), vp, C.c_int, vp, vp]),
 }
 
 _lib = None

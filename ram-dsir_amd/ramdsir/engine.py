@@ -246,7 +246,11 @@ class Act:
         self.g_written = False
         self.needs_grad = False       # a tensor without a producer in the plan (a module's input) whose gradient is wanted all the same
         G = plan.G
-        if norm is not None:
+        if norm is not None and plan.frozen_bn:
+            # coefficients from the running statistics (rd_bn_eval_coeffs): no sums, no saved statistics, no backward
+            self.scale, self.shift = plan.alloc_f32(G * Cc), plan.alloc_f32(G * Cc)
+            self.stats = self.bstats = self.mean = self.invstd = self.P = self.Q = self.R = None
+        elif norm is not None:
             self.stats = plan.alloc_stat(G * L.STAT_SLOTS * Cc * 2)
             self.bstats = plan.alloc_stat(G * L.STAT_SLOTS * Cc * 2)
             self.scale, self.shift = plan.alloc_f32(G * Cc), plan.alloc_f32(G * Cc)
@@ -311,14 +315,21 @@ class Plan:
     """Buffers + launch lists for one batch geometry (N images in G groups at H x W)."""
 
     def __init__(self, bank, dtype, N, gstart, slope=0.0, training=True, options=None, fused_step=False, pad_narrow=False,
-                 side_cus=0, conv_cus=0, dgrad_cus=0):
+                 side_cus=0, conv_cus=0, dgrad_cus=0, frozen_bn=False):
         """options: a full option set (tuning.options(...)); None: the process-wide one.  The facts of THIS plan are arguments:
         fused_step   a plan of the fused training step.  False (a module called on its own, an eval plan) never folds a BatchNorm
                      finalize and stores neither y = up2(t) nor act(bn(z)) / dz, whatever the options say
         pad_narrow   pad the dlogits of the output convs to one 16-byte slot
         side_cus     >0: compute-unit budget of the weight-gradient launches (they run on a side stream)
         conv_cus     >0: ... of this plan's persistent conv launches (a side-lane plan)
-        dgrad_cus    >0: ... of its >= 64-channel gradient launches only (tuning.py dgrad_cus)"""
+        dgrad_cus    >0: ... of its >= 64-channel gradient launches only (tuning.py dgrad_cus)
+        frozen_bn    an inference plan (ramdsir/infer.py): BatchNorm in eval mode with coefficients that ONE rd_bn_eval_coeffs launch
+                     per pass derives from the running statistics of all sites (self.bn_sites).  The forward list then holds the conv
+                     and pool launches only: no statistics (rd_conv_t.stats NULL, no rd_up_stats), no finalize, no rd_bn_apply"""
+        if frozen_bn and (training or fused_step or len(gstart) != 2):
+            raise ValueError('a frozen-BatchNorm plan is a forward-only plan with one group (training=False, fused_step=False)')
+        self.frozen_bn = bool(frozen_bn)
+        self.bn_sites = []                      # frozen_bn: (gamma, beta, running_mean, running_var, scale, shift, C) per site, in launch order
         opt = T.options() if options is None else options
         self.bank, self.dtype = bank, dtype
         self.dt = L.RD_BF16 if dtype == torch.bfloat16 else L.RD_F32
@@ -535,7 +546,10 @@ class Plan:
             else:
                 self._fwd_conv(node)
                 if node.out.norm is not None:
-                    self._fwd_bn_site(node)
+                    if self.frozen_bn:
+                        self._frozen_bn_site(node)
+                    else:
+                        self._fwd_bn_site(node)
         self._fwd_unclaimed_finalizes()
         if not self.training:
             return
@@ -575,7 +589,7 @@ class Plan:
         p.N, p.H, p.W, p.Cin, p.Cout = o.N, o.H, o.W, node.Cin, node.Cout
         p.G, p.gstart = self.G, self.gs_arr
         p.emode, p.out = 0, o.buf.data_ptr()
-        p.stats = self.stat_ptr(o.stats) if (o.norm is not None and not o.up) else None
+        p.stats = self.stat_ptr(o.stats) if (o.norm is not None and not o.up and not self.frozen_bn) else None
         if ((self.store_operands & 1) and self.training and self.dtype == torch.bfloat16 and node.taps == 9 and node.Cin >= self.store_min_c
                 and lib.rd_conv_honours_src_out(C.byref(p), dt)):
             for i, (a, mode, n_off, g_fixed) in enumerate(node.inputs):
@@ -627,6 +641,14 @@ class Plan:
             Hh, Ww = (2 * o.H, 2 * o.W) if o.up else (o.H, o.W)
             self.fwd.append((lib.rd_bn_apply, (src.data_ptr(), None, o.a_buf.data_ptr(), o.scale.data_ptr(), None, o.shift.data_ptr(),
                                                self.slope, o.N, Hh, Ww, o.C, self.G, self.gs_arr, dt)))
+
+    def _frozen_bn_site(self, node):
+        """frozen_bn: nothing is launched behind the conv; the site joins the table of rd_bn_eval_coeffs."""
+        o = node.out
+        if o.norm.kind != 'bn':
+            raise ValueError('a frozen-BatchNorm plan needs running statistics: norm=%r has none' % o.norm.kind)
+        self.bn_sites.append((o.norm.param(0, 'weight'), o.norm.param(0, 'bias'), o.norm.buf(0, 'running_mean'),
+                              o.norm.buf(0, 'running_var'), o.scale, o.shift, o.C))
 
     def _fwd_unclaimed_finalizes(self):
         """A folded forward finalize exists only inside the launch that TAKES it (_take_fwd_fin, as owner).  A BatchNorm site whose readers

@@ -185,6 +185,19 @@ def threshold(logits, recs, n, nbytes):
     return mask
 
 
+def threshold_nhwc(logits, recs, n, nbytes):
+    """Stage a on the plan's own logits: (n, S, S, cstride) fp32 / bf16 NHWC on the device, channel 0 the cup and 1 the disc -> packed
+    uint8 masks of the records' native sizes (rd_val_threshold_nhwc: the bits of threshold() on the fp32 NCHW copy)."""
+    if logits.dtype not in (torch.float32, torch.bfloat16) or logits.dim() != 4 or logits.shape[0] != n or logits.shape[3] < 2 \
+            or not logits.is_contiguous():
+        raise ValueError('--fused_val: expected contiguous NHWC logits (B, H, W, >= 2) in fp32 / bf16; got %s %s' % (logits.dtype, tuple(logits.shape)))
+    mask = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
+    dt = L.RD_BF16 if logits.dtype == torch.bfloat16 else L.RD_F32
+    L.check(L.lib().rd_val_threshold_nhwc(L.ptr(logits), dt, logits.shape[3], n, logits.shape[1], logits.shape[2], recs, L.ptr(mask), nbytes,
+                                          _stream()), 'rd_val_threshold_nhwc')
+    return mask
+
+
 def post(mask, recs, n, nbytes, gt=None, counts=None):
     """Stages b and c: packed uint8 masks -> post-processed masks (a new buffer); with gt and counts (int32 (slots, 2, 3)) the
     planes' |post|, |gt|, |post & gt| are added to counts."""
@@ -206,9 +219,26 @@ class ValResident:
     def __init__(self, inputs, gt, gt_offs, sizes, ids):
         self.inputs, self.gt, self.gt_offs, self.sizes, self.ids = inputs, gt, gt_offs, sizes, ids
         self.nbytes = inputs.numel() * 4 + gt.numel()
+        self.inputs_nhwc = None                             # keep_nhwc(): the inputs as the fused forward reads them
 
     def __len__(self):
         return len(self.sizes)
+
+    def keep_nhwc(self, dtype, cstride=None):
+        """Also keep the inputs as NHWC [n][S][S][cstride] in the storage dtype `dtype` (cstride: default the channel count; channels
+        past it are zero): converted ONCE by rd_nchw_to_nhwc, the conversion the Encoder module applies to every batch, so EvalForward's
+        first conv sees the bits the module's sees (--fused_val).  Replaces an earlier copy."""
+        n, c, S, S2 = self.inputs.shape
+        cs = c if cstride is None else int(cstride)
+        if self.inputs_nhwc is not None:
+            self.nbytes -= self.inputs_nhwc.numel() * self.inputs_nhwc.element_size()
+        out = torch.zeros((n, S, S2, cs), dtype=dtype, device=self.inputs.device)
+        if n:
+            L.check(L.lib().rd_nchw_to_nhwc(L.ptr(self.inputs), L.ptr(out), n, c, S, S2, cs, L.RD_BF16 if dtype == torch.bfloat16 else L.RD_F32,
+                                            _stream()), 'rd_nchw_to_nhwc')
+        self.inputs_nhwc = out
+        self.nbytes += out.numel() * out.element_size()
+        return out
 
 
 def _mask_size(path):
@@ -216,10 +246,12 @@ def _mask_size(path):
         return im.size
 
 
-def preload(testset, workers=8, device=None, batch_size=8):
+def preload(testset, workers=8, device=None, batch_size=8, nhwc_dtype=None):
     """Runs `testset` (dataset.fundus.Fundus, split 'test', Resize + Normalize) once, with at most 16 threads, and keeps what
     validation needs on the device.  Returns None -- after printing one line -- when that would take more than half of the free
-    device memory.  The threads touch no global random state (the transforms of the test split draw nothing)."""
+    device memory.  The threads touch no global random state (the transforms of the test split draw nothing).
+    nhwc_dtype (torch.float32 / torch.bfloat16; --fused_val): also keep the inputs in the layout EvalForward reads
+    (ValResident.keep_nhwc); None keeps nothing more."""
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     n = len(testset)
     nw = min(16, max(1, int(workers)))
@@ -229,7 +261,7 @@ def preload(testset, workers=8, device=None, batch_size=8):
     S = 256
     px = sorted((h * w for h, w in sizes), reverse=True)
     scratch = sum(px[:batch_size]) * (2 + 2 + 16) + 64 * batch_size          # masks, post, parents + counts of the largest batch
-    need = n * 3 * S * S * 4 + sum(2 * p for p in px) + scratch
+    need = n * 3 * S * S * 4 + sum(2 * p for p in px) + scratch + (n * 3 * S * S * (2 if nhwc_dtype == torch.bfloat16 else 4) if nhwc_dtype is not None else 0)
     free = torch.cuda.mem_get_info(device)[0]
     if need > MEM_SHARE * free:
         print('gpu_val: the resident test set needs %.2f GB, more than %d %% of the %.2f GB free on %s: validating on the host'
@@ -251,13 +283,19 @@ def preload(testset, workers=8, device=None, batch_size=8):
             gt[gt_offs[i]:gt_offs[i] + orig.numel()].copy_(orig.to(torch.uint8).reshape(-1))
     if inputs is None:
         inputs = torch.empty((0, 3, S, S), dtype=torch.float32, device=device)
-    return ValResident(inputs, gt, gt_offs, sizes, [l for l in testset.id_path])
+    res = ValResident(inputs, gt, gt_offs, sizes, [l for l in testset.id_path])
+    if nhwc_dtype is not None:
+        res.keep_nhwc(nhwc_dtype)
+    return res
 
 
-def validate(encoder, seg_decoder, res, batch_size=8, keep=None):
+def validate(encoder, seg_decoder, res, batch_size=8, keep=None, forward=None):
     """One validation pass over the resident set: the forward pass of train.py::test_fundus on batches of `batch_size` in list order,
     stages a-c per batch, one device-to-host copy.  Returns [(cup dice, disc dice)] per image.  keep: a list that receives
-    (thresholded masks, post-processed masks, records) of every batch (tests)."""
+    (thresholded masks, post-processed masks, records) of every batch (tests).  forward: an infer.EvalForward over the same
+    parameters (--fused_val): the forward pass is its launch list instead of the modules, the same masks and counts."""
+    if forward is not None:
+        return _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep)
     n = len(res)
     counts = torch.zeros((max(n, 1), 2, 3), dtype=torch.int32, device=res.inputs.device)
     encoder.eval()
@@ -268,6 +306,33 @@ def validate(encoder, seg_decoder, res, batch_size=8, keep=None):
             logits = seg_decoder(encoder(res.inputs[b0:b1]))
             recs, nbytes = image_records(res.sizes[b0:b1], res.gt_offs[b0:b1], range(b0, b1))
             mask = threshold(logits, recs, b1 - b0, nbytes)
+            out = post(mask, recs, b1 - b0, nbytes, res.gt, counts)
+            if keep is not None:
+                keep.append((mask, out, recs))
+    c = counts.cpu().tolist()                               # the pass's only synchronisation
+    return [(dice_from_counts(*c[i][0]), dice_from_counts(*c[i][1])) for i in range(n)]
+
+
+def _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep):
+    """validate() with the forward pass as EvalForward's launch list: refresh() once, then per batch the resident NHWC slice is copied
+    into the plan's input, ONE rd_run_list call, and stage a reads the plan's logits in place (rd_val_threshold_nhwc).  Stages b and c,
+    the counts and the copy that ends the pass are validate()'s."""
+    n = len(res)
+    S, S2 = res.inputs.shape[2:4]
+    x0 = forward.input(min(batch_size, max(n, 1)), S, S2)
+    if res.inputs_nhwc is None or res.inputs_nhwc.dtype != x0.dtype or res.inputs_nhwc.shape[3] != x0.shape[3]:
+        res.keep_nhwc(x0.dtype, x0.shape[3])                # (a resident set preloaded without nhwc_dtype, or for another layout)
+    counts = torch.zeros((max(n, 1), 2, 3), dtype=torch.int32, device=res.inputs.device)
+    encoder.eval()                                          # the flags the module path leaves behind
+    seg_decoder.eval()
+    with torch.no_grad():
+        forward.refresh()
+        for b0 in range(0, n, batch_size):
+            b1 = min(b0 + batch_size, n)
+            forward.input(b1 - b0, S, S2).copy_(res.inputs_nhwc[b0:b1])
+            logits = forward.run(b1 - b0, S, S2)
+            recs, nbytes = image_records(res.sizes[b0:b1], res.gt_offs[b0:b1], range(b0, b1))
+            mask = threshold_nhwc(logits, recs, b1 - b0, nbytes)
             out = post(mask, recs, b1 - b0, nbytes, res.gt, counts)
             if keep is not None:
                 keep.append((mask, out, recs))

@@ -139,6 +139,28 @@ def stack(volume, frames):
     return out
 
 
+def stack_nhwc(volume, frames, out):
+    """volume (D, H, W) fp32 on the device -> the batch of predict_volume straight into `out`, the NHWC storage-dtype input
+    (len(frames), H, W, cstride) of an EvalForward plan (rd_vol_stack_nhwc: the bits rd_nchw_to_nhwc makes of stack())."""
+    D, H, W = volume.shape
+    if out.dtype not in (torch.float32, torch.bfloat16) or tuple(out.shape[:3]) != (len(frames), H, W) or not out.is_contiguous():
+        raise ValueError('--fused_val: the plan input must be contiguous NHWC %s in fp32 / bf16; got %s %s'
+                         % ((len(frames), H, W, 'cstride'), out.dtype, tuple(out.shape)))
+    L.check(L.lib().rd_vol_stack_nhwc(L.ptr(volume), D, H, W, _frames(frames), len(frames), L.ptr(out),
+                                      L.RD_BF16 if out.dtype == torch.bfloat16 else L.RD_F32, out.shape[3], _stream()), 'rd_vol_stack_nhwc')
+
+
+def argmax_nhwc(logits, frames, gt_empty, pred, shape):
+    """logits (B, H, W, cstride) fp32 / bf16 NHWC on the device -> the slices `frames` of pred (rd_vol_argmax_nhwc: argmax()'s bytes)."""
+    D, H, W = shape
+    if logits.dtype not in (torch.float32, torch.bfloat16) or tuple(logits.shape[:3]) != (len(frames), H, W) or logits.shape[3] < 2 \
+            or not logits.is_contiguous():
+        raise ValueError('--fused_val: expected contiguous NHWC logits %s in fp32 / bf16; got %s %s'
+                         % ((len(frames), H, W, '>= 2'), logits.dtype, tuple(logits.shape)))
+    L.check(L.lib().rd_vol_argmax_nhwc(L.ptr(logits), L.RD_BF16 if logits.dtype == torch.bfloat16 else L.RD_F32, logits.shape[3], len(frames),
+                                       H, W, _frames(frames), L.ptr(gt_empty), D, L.ptr(pred), _stream()), 'rd_vol_argmax_nhwc')
+
+
 def argmax(logits, frames, gt_empty, pred, shape):
     """logits (B, 2, H, W) fp32 on the device -> the slices `frames` of pred (a flat uint8 view of the (D, H, W) prediction)."""
     D, H, W = shape
@@ -265,10 +287,14 @@ def preload(data_dir, domain_name, batch_size=8, workers=8, device=None):
     return VolResident(volumes, gt, gt_empty, shapes, files, scratch)
 
 
-def validate(encoder, seg_decoder, res, batch_size=8, keep=None):
+def validate(encoder, seg_decoder, res, batch_size=8, keep=None, forward=None):
     """One validation pass over the resident volumes: per volume the batches of predict_volume through the modules (eval mode,
     no_grad), then the post-processing of all volumes, one device-to-host copy.  Returns the Dice of every volume in list order.
-    keep: a dict that receives the prediction and the post-processed volumes as numpy arrays (tests)."""
+    keep: a dict that receives the prediction and the post-processed volumes as numpy arrays (tests).  forward: an
+    infer.EvalForward over the same parameters (--fused_val): the forward pass is its launch list instead of the modules, the same
+    volumes and counts."""
+    if forward is not None:
+        return _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep)
     n = len(res)
     counts = torch.zeros((max(n, 1), 3), dtype=torch.int32, device=res.gt.device)
     encoder.eval()
@@ -280,6 +306,35 @@ def validate(encoder, seg_decoder, res, batch_size=8, keep=None):
             for frames in frame_batches(res.shapes[i][0], batch_size):
                 logits = seg_decoder(encoder(stack(res.volumes[i], frames)))
                 argmax(logits, frames, res.gt_empty[i], pred, res.shapes[i])
+        groups = [(volume_records(res.shapes[a:b], res.offs[a:b], slots=range(a, b))[0], b - a) for a, b in post_groups(res.shapes)]
+        ws_bytes = max([L.lib().rd_vol_post_workspace(recs, m) for recs, m in groups] or [0])
+        workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=res.gt.device)
+        for recs, m in groups:
+            post(res.pred, res.post, recs, m, res.gt, counts, workspace)
+    c = counts.cpu().tolist()                               # the pass's only synchronisation
+    if keep is not None:
+        keep['pred'] = [res.pred[res.offs[i]:res.offs[i + 1]].cpu().numpy().reshape(res.shapes[i]) for i in range(n)]
+        keep['post'] = [res.post[res.offs[i]:res.offs[i + 1]].cpu().numpy().reshape(res.shapes[i]) for i in range(n)]
+        keep['counts'] = c
+    return [dice_from_counts(*c[i]) for i in range(n)]
+
+
+def _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep):
+    """validate() with the forward pass as EvalForward's launch list: refresh() once, then per batch rd_vol_stack_nhwc writes the plan's
+    input, ONE rd_run_list call, rd_vol_argmax_nhwc reads the plan's logits in place.  The rest is validate()'s."""
+    n = len(res)
+    counts = torch.zeros((max(n, 1), 3), dtype=torch.int32, device=res.gt.device)
+    encoder.eval()                                          # the flags the module path leaves behind
+    seg_decoder.eval()
+    with torch.no_grad():
+        forward.refresh()
+        zero(res.pred)                                      # slices that no batch reaches, and empty slots, stay zero
+        for i in range(n):
+            pred = res.pred[res.offs[i]:res.offs[i + 1]]
+            _, H, W = res.shapes[i]
+            for frames in frame_batches(res.shapes[i][0], batch_size):
+                stack_nhwc(res.volumes[i], frames, forward.input(len(frames), H, W))
+                argmax_nhwc(forward.run(len(frames), H, W), frames, res.gt_empty[i], pred, res.shapes[i])
         groups = [(volume_records(res.shapes[a:b], res.offs[a:b], slots=range(a, b))[0], b - a) for a, b in post_groups(res.shapes)]
         ws_bytes = max([L.lib().rd_vol_post_workspace(recs, m) for recs, m in groups] or [0])
         workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=res.gt.device)

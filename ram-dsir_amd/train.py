@@ -94,6 +94,9 @@ def parse_args(argv=None):
     p.add_argument('--gpu_val_volumes', action='store_true',
                    help='prostate: keep the held-out site\'s volumes in device memory and build the 2.5-D batches, take the argmax, keep '
                         'the largest 3-D component and count for the Dice as HIP kernels; the reported numbers are those of the host path')
+    p.add_argument('--fused_val', action='store_true',
+                   help='with --gpu_val / --gpu_val_volumes (--norm bn): the validation forward pass as one HIP launch list per batch '
+                        '(ramdsir/infer.py EvalForward) instead of the drop-in modules; the same masks, counts and CSV lines')
     p.add_argument('--tb_images', type=int, nargs='?', const=100, default=0, metavar='N',
                    help='also write the reference\'s TensorBoard image grids (input, RAM-mixed input, restored image, predictions, ground '
                         'truth) of rank 0\'s batch every N iterations (100 as in the reference when N is omitted), composed by one HIP '
@@ -182,17 +185,18 @@ def _val_testset(data_dir, datasetTest):
 _VAL_GPU = {}
 
 
-def test_fundus_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='fundus'):
+def test_fundus_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='fundus', forward=None):
     """test_fundus with everything after the forward pass on the GPU (--gpu_val; ramdsir/gpu_val.py, csrc/val_post.hip): the same
     batches in list order through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.
-    The resident test set is main()'s preload (or is made here at the first call)."""
+    The resident test set is main()'s preload (or is made here at the first call).  forward (--fused_val): the infer.EvalForward that
+    runs the forward pass instead of the modules."""
     from ramdsir import gpu_val
     key = (data_dir, datasetTest)
     if key not in _VAL_GPU:
         _VAL_GPU[key] = gpu_val.preload(_val_testset(data_dir, datasetTest), batch_size=batch_size)
         if _VAL_GPU[key] is None:
             raise RuntimeError('--gpu_val: the test set does not fit in device memory')
-    dices = gpu_val.validate(encoder, seg_decoder, _VAL_GPU[key], batch_size)
+    dices = gpu_val.validate(encoder, seg_decoder, _VAL_GPU[key], batch_size, forward=forward)
     cup = disc = 0.0
     n = 0
     for c, d in dices:
@@ -222,10 +226,11 @@ def test_prostate(encoder, seg_decoder, epoch, data_dir, datasetTest, output_pat
 _VAL_VOL = {}
 
 
-def test_prostate_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='prostate'):
+def test_prostate_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='prostate', forward=None):
     """test_prostate on the resident volumes (--gpu_val_volumes; ramdsir/gpu_val_volumes.py, csrc/val_volume.hip): the same batches
     through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.  The resident
-    volumes are main()'s preload (or are made here at the first call)."""
+    volumes are main()'s preload (or are made here at the first call).  forward (--fused_val): the infer.EvalForward that runs the
+    forward pass instead of the modules."""
     from ramdsir import gpu_val_volumes
     from utils.prostate_eval import DOMAIN_LIST
     key = (data_dir, datasetTest)
@@ -234,7 +239,7 @@ def test_prostate_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output
         if _VAL_VOL[key] is None:
             raise RuntimeError('--gpu_val_volumes: the volumes do not fit in device memory')
     val_dice = 0.0
-    for d in gpu_val_volumes.validate(encoder, seg_decoder, _VAL_VOL[key], batch_size):
+    for d in gpu_val_volumes.validate(encoder, seg_decoder, _VAL_VOL[key], batch_size, forward=forward):
         val_dice += d
     val_dice = val_dice / max(len(_VAL_VOL[key]), 1)
     print('val_dice : {}'.format(val_dice))
@@ -296,6 +301,10 @@ def main(args):
         raise ValueError('--tb_images takes a positive interval, got %d' % args.tb_images)
     if args.gpu_val_volumes and args.dataset != 'prostate':
         raise ValueError('--gpu_val_volumes covers the in-training Prostate validation only; --dataset %s has --gpu_val' % args.dataset)
+    if args.fused_val and not (args.gpu_val or args.gpu_val_volumes):
+        raise ValueError('--fused_val is the forward pass of the resident validation: it needs --gpu_val (fundus) or --gpu_val_volumes (prostate)')
+    if args.fused_val and args.norm != 'bn':
+        raise ValueError('--fused_val freezes BatchNorm on its running statistics: --norm %s has none (validate through the modules)' % args.norm)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -342,11 +351,19 @@ def main(args):
         # the held-out test set, decoded once and kept on this GPU (ramdsir/gpu_val.py); the host path if it does not fit
         from ramdsir import gpu_val
         t0 = time.time()
-        val_set = gpu_val.preload(_val_testset(data_root, args.test_domain_idx), workers=preload_workers, batch_size=args.test_batch_size)
+        nhwc = None
+        if args.fused_val:                                  # the inputs also in the layout and dtype the fused forward reads
+            from ramdsir import modules
+            nhwc = modules.storage_dtype()
+        val_set = gpu_val.preload(_val_testset(data_root, args.test_domain_idx), workers=preload_workers, batch_size=args.test_batch_size,
+                                  nhwc_dtype=nhwc)
         if val_set is not None:
             _VAL_GPU[(data_root, args.test_domain_idx)] = val_set
             validate = test_fundus_gpu
-            print('gpu_val: %d test images, %.3f GB resident, preloaded in %.1f s' % (len(val_set), val_set.nbytes / 1e9, time.time() - t0))
+            print('gpu_val: %d test images, %.3f GB resident%s, preloaded in %.1f s'
+                  % (len(val_set), val_set.nbytes / 1e9, '' if nhwc is None else ' (%.3f GB of it the NHWC %s inputs of --fused_val)'
+                     % (val_set.inputs_nhwc.numel() * val_set.inputs_nhwc.element_size() / 1e9, 'bf16' if nhwc == torch.bfloat16 else 'fp32'),
+                     time.time() - t0))
         else:
             rng_state = torch.get_rng_state()               # the loader's draw has been taken above
             _val_resources(data_root, args.test_domain_idx, args.test_batch_size)
@@ -392,6 +409,22 @@ def main(args):
     trainer = Trainer(encoder, seg_decoder, rec_decoder, bsl[:len(domain_idx_list)], H, W, dataset=args.dataset,
                            consistency=cons, lambda_rec=args.lambda_rec, lr=args.lr, total_iters=total_iters,
                            dtype=torch.bfloat16 if (args.dtype or ('bf16' if args.norm == 'bn' else 'f32')) == 'bf16' else torch.float32)
+
+    if rank == 0 and args.fused_val:
+        # the validation forward pass as one launch list over the trainer's own parameter arena (ramdsir/infer.py); only where the
+        # resident validation is in use (a test set that did not fit validates on the host, through the modules)
+        if validate is test_fundus_gpu or validate_prostate is test_prostate_gpu:
+            import functools
+            from ramdsir.infer import EvalForward
+            fused_forward = EvalForward.from_trainer(trainer)
+            validate = functools.partial(test_fundus_gpu, forward=fused_forward) if validate is test_fundus_gpu else validate
+            validate_prostate = functools.partial(test_prostate_gpu, forward=fused_forward) if validate_prostate is test_prostate_gpu \
+                else validate_prostate
+            print('fused_val: validation forward as one launch list per batch, %s storage, %s' % (
+                'bf16' if fused_forward.dtype == torch.bfloat16 else 'fp32',
+                'its own weight pack (one repack per pass)' if fused_forward.owns_pack else "the step's weight pack (no repack)"))
+        else:
+            print('fused_val: the resident validation is not in use: validating through the modules')
 
     # --tb_images: one writer thread owns the event file (scalars go through its queue too, so the records keep the order of the
     # calls); without the flag the direct writer, record for record what it always wrote

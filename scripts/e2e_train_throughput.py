@@ -26,6 +26,7 @@ ap.add_argument('--workers', type=int, default=8)
 ap.add_argument('--dtype', default='bf16')
 ap.add_argument('--gpu_data', action='store_true')
 ap.add_argument('--gpu_val', action='store_true')
+ap.add_argument('--fused_val', action='store_true')
 ap.add_argument('--n_test', type=int, default=8)
 ap.add_argument('--tb_images', type=int, default=0)
 ap.add_argument('--tree', default=None)
@@ -40,6 +41,7 @@ with tempfile.TemporaryDirectory() as out_tmp:
            '--test_domain_idx', '0', '--ram', '--rec', '--is_out_domain', '--consistency', '--consistency_type', 'kd', '--save_path',
            os.path.join(out_tmp, 'out'), '--epochs', '1000', '--max_iters', str(a.iters), '--num_workers', str(a.workers), '--log_every', '50',
            '--dtype', a.dtype] + (['--gpu_data'] if a.gpu_data else []) + (['--gpu_val'] if a.gpu_val else []) + \
+          (['--fused_val'] if a.fused_val else []) + \
           (['--tb_images', str(a.tb_images)] if a.tb_images else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     out = r.stdout.decode()
