@@ -736,6 +736,45 @@ typedef struct {
 int64_t rd_tb_grids_workspace(int n_grids);
 int rd_tb_grids(const rd_tb_grid_t* grids_host, int n_grids, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-step record stream (train.py --tb_every_iter / --tb_health, ramdsir/step_log.py), csrc/step_log.hip: the reference writes its
+ * seven scalars -- lr, loss/loss_{bce,ce}_1, loss/loss_dice_1, loss/loss_{bce,ce}_2, loss/loss_dice_2, loss/loss_consistency,
+ * loss/loss_rec -- at EVERY iteration (code/train.py:298-304 Fundus, :467-473 Prostate), reading each loss with .item().  Here one call
+ * behind a step appends one row of RD_LOG_ROW floats to a device-resident ring and the host drains the ring where it synchronises
+ * anyway.  Row layout (float32 words):
+ *   [0, 8)    losses[8]   (rd_seg_loss's losses_out)
+ *   [8, 12)   hyper[4]    (rd_adam_step's hyper_out: word 8 is the lr of the step, word 11 its iteration number)
+ *   [12, 28)  rec_mse[n_rec], the remaining slots 0 (n_rec <= RD_LOG_MAX_REC)
+ *   [28, 31)  gradient norms of the three Adam groups (code/train.py:573-576: encoder, seg decoder, rec decoder), elements
+ *             [range[g], range[g + 1]) of `grads`: (float)sqrt(sum of g * g), the sum in fp64 over the FINITE elements
+ *   [31]      the number of non-finite (NaN, +-Inf) elements of [range[0], range[3]), as a float (exact: range[3] - range[0] <= 2^24)
+ * grads == NULL: no health pass, words 28..31 are 0 and `partial` is not used.  The row goes to ring + row * RD_LOG_ROW; the caller
+ * owns the row counter.  The health pass has no reference counterpart.  It is a pure function of the data: group g is cut into chunks
+ * of RD_LOG_CHUNK elements from range[g] on, chunk c of the call (groups in order) is summed by workgroup c in a fixed order into
+ * partial[c] = {double sum, int64 count}; a second launch of one workgroup adds the partials of a group, each lane of a wave its
+ * indices lane, lane + 64, ... in ascending order, then the 64 lanes in a fixed tree -- no atomics, nothing depends on which
+ * workgroup finishes first.  Wide loads are used on the 16-byte-aligned part of a chunk, whatever the alignment of grads + range[g].
+ * partial: rd_step_log_workspace(range[3] - range[0]) bytes, 8-byte aligned, contents irrelevant before and after.  At most two
+ * launches on `stream`; allocates nothing, synchronises nothing, copies nothing.  Returns, before anything is launched: -1 a null
+ * descriptor / losses / rec_mse / hyper / ring (or partial, with grads), -2 row outside [0, rows), -3 n_rec outside
+ * [0, RD_LOG_MAX_REC], -4 a negative or decreasing range or one of more than 2^24 elements. */
+#define RD_LOG_ROW 32
+#define RD_LOG_MAX_REC 16
+#define RD_LOG_CHUNK 4096
+typedef struct {
+    const float* losses;        /* device [8] */
+    const float* rec_mse;       /* device [n_rec] */
+    const float* hyper;         /* device [4] */
+    const float* grads;         /* device arena, or NULL */
+    int64_t range[4];           /* element offsets into grads */
+    float* ring;                /* device [rows][RD_LOG_ROW] */
+    int32_t rows, row;
+    int32_t n_rec;
+    int32_t pad_;
+    void* partial;
+} rd_step_log_t;
+int rd_step_log(const rd_step_log_t* p, void* stream);
+int64_t rd_step_log_workspace(int64_t n);
+
 /* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
  * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
  * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */

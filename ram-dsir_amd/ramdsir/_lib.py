@@ -139,6 +139,15 @@ class RdTbGrid(C.Structure):
                 ('normalize', i32), ('slot', i32)]
 
 
+LOG_ROW, LOG_MAX_REC, LOG_CHUNK = 32, 16, 4096                      # RD_LOG_ROW, RD_LOG_MAX_REC, RD_LOG_CHUNK
+
+
+class RdStepLog(C.Structure):
+    """rd_step_log_t (include/ramdsir.h): one row of the per-step record ring."""
+    _fields_ = [('losses', fp), ('rec_mse', fp), ('hyper', fp), ('grads', fp), ('range', i64 * 4), ('ring', fp), ('rows', i32), ('row', i32),
+                ('n_rec', i32), ('pad_', i32), ('partial', vp)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -220,6 +229,8 @@ _SIGS = {
     'rd_op_code': (C.c_int, [C.c_char_p]),
     'rd_tb_grids_workspace': (i64, [C.c_int]),
     'rd_tb_grids': (C.c_int, [C.POINTER(RdTbGrid), C.c_int, vp, i64, vp]),
+    'rd_step_log': (C.c_int, [C.POINTER(RdStepLog), vp]),
+    'rd_step_log_workspace': (i64, [i64]),
     'rd_crc32c': (C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),

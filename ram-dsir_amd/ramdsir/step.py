@@ -457,11 +457,15 @@ class TrainStep:
 
     def loss_dict(self):
         """Synchronises.  Names follow the tensorboard scalars of train.py:298-304."""
-        l = self.losses.cpu().tolist()
-        r = self.rec_mse.cpu().tolist()
-        seg = 'bce' if self.dataset == 'fundus' else 'ce'
-        return {'loss_%s_1' % seg: l[0], 'loss_dice_1': l[1], 'loss_%s_2' % seg: l[2], 'loss_dice_2': l[3],
-                'loss_consistency': l[4], 'rec': r, 'loss': l[5] + self.lambda_rec * sum(r)}
+        return loss_dict_of(self.dataset, self.lambda_rec, self.losses.cpu().tolist(), self.rec_mse.cpu().tolist())
+
+
+def loss_dict_of(dataset, lambda_rec, l, r):
+    """The loss record of one step from the two lists TrainStep.loss_dict() reads back (losses[8] and rec_mse as Python floats): the
+    one place where the names and the total are formed, shared with the rows of the per-step ring (step_log.py)."""
+    seg = 'bce' if dataset == 'fundus' else 'ce'
+    return {'loss_%s_1' % seg: l[0], 'loss_dice_1': l[1], 'loss_%s_2' % seg: l[2], 'loss_dice_2': l[3],
+            'loss_consistency': l[4], 'rec': r, 'loss': l[5] + lambda_rec * sum(r)}
 
 
 def make_bank(device, in_channels=3, n=16, num_classes=2, num_domains=3):

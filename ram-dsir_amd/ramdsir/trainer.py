@@ -28,7 +28,7 @@ class FusedTrainer:
                               options=dict(side_cus=0, rec_cus=0) if use_graph else None)
         self.ts.wpack.refresh()
         self._primed, self._graphs, self._announced = False, bool(use_graph), None
-        self._tb, self._tb_pending = None, None
+        self._tb, self._tb_pending, self._tb_hook, self._log = None, None, None, None
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -64,6 +64,7 @@ class FusedTrainer:
         pipelined = next_batch is not None and not self._graphs
         if pipelined:
             self.ts.load_raw_next(*next_batch[:3])
+        self._arm_after_step()
         self._step()
         if pipelined:
             self.ts.load_target(next_batch[3])            # after the step has been enqueued: its loss still reads the current mask
@@ -84,7 +85,48 @@ class FusedTrainer:
 
         def hook(slot):
             self._tb_pending = self._tb.enqueue(tb_images.train_step_sources(ts, slot))
-        ts.arm_after_step(hook)
+        self._tb_hook = hook
+
+    def _arm_after_step(self):
+        """TrainStep.arm_after_step holds ONE one-shot hook; the image grids (armed for single steps) and the step log (every step, once
+        enabled) share it: one closure per step runs whichever of the two apply.  Nothing is armed when neither does."""
+        tb, self._tb_hook = self._tb_hook, None
+        log = self._log
+        if tb is None and log is None:
+            return
+
+        def hook(slot):
+            if log is not None:
+                log.append(torch.cuda.current_stream().cuda_stream)
+            if tb is not None:
+                tb(slot)
+        self.ts.arm_after_step(hook)
+
+    def enable_step_log(self, health=False, rows=256):
+        """From now on every step() appends one row to a device-resident ring (ramdsir/step_log.py, rd_step_log): the losses, the lr and
+        the iteration number of the step and, with health=True, the gradient norm of each of the three Adam groups (code/train.py:573-576)
+        and the number of non-finite gradient elements.  The row is written on the main stream behind the step's last launch -- behind
+        the join of all lanes, Adam and the repack, in front of the upload of the next mask (TrainStep.arm_after_step) -- and only
+        reads the step's buffers: training is bit-identical with and without it.  drain_step_log() returns the records.  Not with
+        use_graph=True."""
+        if self._graphs:
+            raise RuntimeError('enable_step_log: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        from . import step_log
+        ts, b = self.ts, self.bank
+        r = [b.module_range['enc'][0], b.module_range['enc'][1], b.module_range['dec'][1], b.module_range['rec'][1]]
+        assert b.module_range['dec'][0] == r[1] and b.module_range['rec'][0] == r[2]
+        self._log = step_log.StepLog(ts.losses, ts.rec_mse, ts.hyper, b.grads if health else None, r if health else None, rows=rows)
+        return self._log
+
+    def step_log_full(self):
+        return self._log is not None and self._log.full()
+
+    def drain_step_log(self):
+        """The records of the steps since the last drain, oldest first: {iteration, losses (the dict of losses()), lr, norms, nonfinite}.
+        Synchronises.  Data parallel: collective, the loss columns are the mean over the ranks (what losses() returns for one step)."""
+        if self._log is None:
+            raise RuntimeError('drain_step_log: enable_step_log() first')
+        return self._log.drain(self.ts.dataset, self.ts.lambda_rec, world=self.world)
 
     def take_tb_images(self):
         """The tb_images.Pending of the last armed step (its images() waits for the copy), once."""

@@ -10,6 +10,8 @@ Differences, all deliberate: (i) RAM runs on the GPU per batch (the DataLoader w
 image and lambda); (ii) the step is a static launch list enqueued ahead of the GPU, so the five loss scalars are read every
 --log_every iterations instead of forcing a device sync every iteration (train.py:298-304) -- and written, under the
 reference's tags, to a TensorBoard event file in <save_path>/log (utils/tfevents.py: tensorboardX is not a dependency);
+--tb_every_iter writes them at every iteration all the same, from a device-resident ring that is read at those iterations
+(ramdsir/step_log.py), and --tb_health adds per-iteration gradient norms and a non-finite count through the same ring;
 (iii) multi-GPU is one process per GPU with an RCCL gradient all-reduce instead of nn.DataParallel; (iv) the tensorboard image
 grids (train.py:306-329, 475-496) are opt-in (--tb_images: composed on the GPU, ramdsir/tb_images.py) and the source-tree snapshot
 (train.py:534-536) is not reproduced.
@@ -101,6 +103,14 @@ def parse_args(argv=None):
                    help='also write the reference\'s TensorBoard image grids (input, RAM-mixed input, restored image, predictions, ground '
                         'truth) of rank 0\'s batch every N iterations (100 as in the reference when N is omitted), composed by one HIP '
                         'call from the step\'s buffers and encoded by a writer thread; off by default')
+    p.add_argument('--tb_every_iter', action='store_true',
+                   help='write the seven TensorBoard scalars at EVERY iteration, as the reference does (train.py:298-304, 467-473), without a '
+                        'host synchronisation per step: one small HIP launch behind each step appends them to a device-resident ring '
+                        '(ramdsir/step_log.py) that is read at the --log_every iterations; --norm bn only; off by default')
+    p.add_argument('--tb_health', action='store_true',
+                   help='per iteration, through the same ring: the gradient norm of each Adam group (health/grad_norm_encoder, _seg_decoder, '
+                        '_rec_decoder) and the number of non-finite gradient elements (health/nonfinite_grads); one console line names the '
+                        'first iteration with non-finite losses or gradients; --norm bn only; off by default')
     return p.parse_args(argv)
 
 
@@ -291,6 +301,37 @@ def make_loaders(args, data_root, world, rank, bsl, domain_idx_list):
     return raw, samplers, loaders, max_len
 
 
+def uses_step_log(args):
+    """Either flag turns the per-step ring on (ramdsir/step_log.py); without both, the run never touches it."""
+    return bool(args.tb_every_iter or args.tb_health)
+
+
+def console_line(iter_num, lr_now, l):
+    return ('iter %d lr %.6f ' % (iter_num, lr_now) + ' '.join('%s %.4f' % (k, v) for k, v in l.items() if k != 'rec')
+            + ' loss_rec %.4f' % (sum(l['rec']) / 4))                 # train.py:304 logs avg/4
+
+
+def scalar_pairs(lr_now, l):
+    """The reference's seven scalars of one iteration (train.py:298-304 / 467-473), in its order."""
+    return [('lr', lr_now)] + [('loss/' + k, v) for k, v in l.items() if k not in ('rec', 'loss')] + [('loss/loss_rec', sum(l['rec']) / 4)]
+
+
+def step_log_pairs(rec, every_iter, health, log_every):
+    """What one drained record (ramdsir/step_log.py) contributes to the event file: the seven scalars at every iteration with
+    --tb_every_iter, otherwise at the --log_every iterations as always; behind them the four health tags with --tb_health."""
+    from ramdsir.step_log import HEALTH_TAGS
+    pairs = scalar_pairs(rec['lr'], rec['losses']) if every_iter or rec['iteration'] % log_every == 0 else []
+    if health:
+        pairs += list(zip(HEALTH_TAGS, rec['norms'] + (float(rec['nonfinite']),)))
+    return pairs
+
+
+def record_is_finite(rec):
+    l = rec['losses']
+    return rec['nonfinite'] == 0 and all(np.isfinite(v) for k, v in l.items() if k != 'rec') and all(np.isfinite(v) for v in l['rec']) \
+        and all(np.isfinite(v) for v in rec['norms'])
+
+
 def main(args):
     if not (args.ram and args.rec):
         # SURVEY.md F5: the reference only runs end-to-end with --ram --rec (train.py:591 / :315 raise otherwise)
@@ -303,6 +344,10 @@ def main(args):
         raise ValueError('--gpu_val_volumes covers the in-training Prostate validation only; --dataset %s has --gpu_val' % args.dataset)
     if args.fused_val and not (args.gpu_val or args.gpu_val_volumes):
         raise ValueError('--fused_val is the forward pass of the resident validation: it needs --gpu_val (fundus) or --gpu_val_volumes (prostate)')
+    step_log = uses_step_log(args)
+    if step_log and args.norm != 'bn':
+        raise ValueError('--tb_every_iter / --tb_health read the fused step\'s device buffers: --norm %s trains through the modules, whose '
+                         'losses are host-visible tensors (use --log_every 1 there)' % args.norm)
     if args.fused_val and args.norm != 'bn':
         raise ValueError('--fused_val freezes BatchNorm on its running statistics: --norm %s has none (validate through the modules)' % args.norm)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -430,6 +475,25 @@ def main(args):
     # calls); without the flag the direct writer, record for record what it always wrote
     Writer = QueuedWriter if args.tb_images else SummaryWriter
     writer = Writer(os.path.join(args.save_path, 'log')) if rank == 0 else None      # train.py:538
+    first_bad = []
+    if step_log:
+        # --tb_every_iter / --tb_health: every step appends one row to a device-resident ring (FusedTrainer.enable_step_log)
+        trainer.enable_step_log(health=args.tb_health)
+
+    def write_step_log():
+        """Drain the ring (collective; synchronises) and write its records in iteration order, with the drain's wall time."""
+        records = trainer.drain_step_log()
+        now = time.time()
+        for rec in records if rank == 0 else ():
+            pairs = step_log_pairs(rec, args.tb_every_iter, args.tb_health, args.log_every)
+            if pairs:
+                writer.add_scalars_at(rec['iteration'], pairs, walltime=now)
+            if args.tb_health and not first_bad and not record_is_finite(rec):
+                first_bad.append(rec['iteration'])
+                print('tb_health: iteration %d is the first with non-finite values (%d non-finite gradient elements, loss %r); the run '
+                      'continues' % (rec['iteration'], rec['nonfinite'], rec['losses']['loss']))
+        return records
+
     previous_best, iter_num = 0.0, 0
     t_mark, it_mark, imgs_per_iter = None, 0, world * sum(bsl[:len(domain_idx_list)])
     for epoch in range(args.epochs):
@@ -464,15 +528,22 @@ def main(args):
                 trainer.arm_tb_images()                 # this step also composes the grids of its batch and starts their copy
             trainer.step(*cur, next_batch=nxt)
             cur = nxt
-            if iter_num % args.log_every == 0:
+            log_now = iter_num % args.log_every == 0
+            if step_log:
+                # the step has appended its row to the device ring; read the ring where the loop synchronises anyway (the logging
+                # iterations), in front of image records (they follow the scalars of their own iteration) and when it is full --
+                # all functions of iter_num alone, so every rank drains at the same iterations (the drain is collective)
+                if log_now or (args.tb_images > 0 and iter_num % args.tb_images == 0) or trainer.step_log_full():
+                    records = write_step_log()
+                    if rank == 0 and log_now:           # printed and written from the same drained row
+                        print(console_line(iter_num, records[-1]['lr'], records[-1]['losses']))
+            elif log_now:
                 l = trainer.losses()                    # collective when world > 1: the mean over the ranks
-            if rank == 0 and iter_num % args.log_every == 0:
-                lr_now = trainer.lr()
-                print('iter %d lr %.6f ' % (iter_num, lr_now) + ' '.join('%s %.4f' % (k, v) for k, v in l.items() if k != 'rec')
-                      + ' loss_rec %.4f' % (sum(l['rec']) / 4))               # train.py:304 logs avg/4
-                # the reference's scalars (train.py:298-304 / 467-473), at the iterations whose losses are read back
-                writer.add_scalars_at(iter_num, [('lr', lr_now)] + [('loss/' + k, v) for k, v in l.items() if k not in ('rec', 'loss')]
-                                      + [('loss/loss_rec', sum(l['rec']) / 4)])
+                if rank == 0:
+                    lr_now = trainer.lr()
+                    print(console_line(iter_num, lr_now, l))
+                    # the reference's scalars (train.py:298-304 / 467-473), at the iterations whose losses are read back
+                    writer.add_scalars_at(iter_num, scalar_pairs(lr_now, l))
             if log_images:                              # behind the scalars of the iteration, in the reference's tag order
                 writer.add_images_at(iter_num, trainer.take_tb_images())
             iter_num += 1
@@ -518,6 +589,8 @@ def main(args):
                   % (epoch, t_train, n_img / max(t_train, 1e-9), t_all - t_train, n_img / max(t_all, 1e-9)))
         if args.max_iters and iter_num >= args.max_iters:
             break
+    if step_log:
+        write_step_log()                                # the rows behind the last logging iteration
     if rank == 0:
         save_checkpoint(os.path.join(args.save_path, 'final_model.pth'), encoder, seg_decoder, rec_decoder)
         print('\nSave Final Model to {}'.format(args.save_path))
