@@ -775,6 +775,41 @@ typedef struct {
 int rd_step_log(const rd_step_log_t* p, void* stream);
 int64_t rd_step_log_workspace(int64_t n);
 
+/* Training-state snapshot (train.py --ckpt_every / --resume, ramdsir/ckpt.py), csrc/snapshot.hip: copies n device ranges to
+ * (direction 0, gather) or from (direction 1, scatter) ONE contiguous staging buffer and leaves two 64-bit checksums per range.  No
+ * reference counterpart: the reference writes its three state_dicts with torch.save (code/train.py:342-360) and never reads one back
+ * into a trainer.  Range i is [ptr, ptr + bytes) on the device and [staging + offset, staging + offset + bytes) in the staging buffer;
+ * bytes is a multiple of 4, ptr, offset and staging are 4-byte aligned, the offsets ascend in table order without overlap and stay
+ * inside staging_bytes.  bytes == 0 is allowed (its sums are 0).  The device ranges of a scatter must not overlap each other (not
+ * checked).  With the little-endian uint32 words w[0 .. bytes / 4) of a range -- the words READ from the range by a gather, the words
+ * WRITTEN to it by a scatter --
+ *     sums[S i] = sum w[k],   sums[S i + 1] = sum (k + 1) w[k]      (both mod 2^64; S = RD_SNAP_SUM_STRIDE: one 128-byte line per
+ * range, of which only these two words are ever written -- same-address atomics are served one after the other, so the pairs of
+ * different ranges sit in different lines; sums_dev holds n * S words)
+ * each workgroup reduces its part and issues one pair of 64-bit integer atomic adds: integer addition commutes, so the sums are the
+ * same bits on every run; no floating point.  Work decomposition: range i is cut into chunks of RD_SNAP_CHUNK bytes from its start
+ * (the last one ragged), chunk0 = the number of chunks of the ranges in front of it; the grid is flat over the total_chunks chunks and
+ * a workgroup finds its range by binary search over chunk0 in table_dev -- the SAME n entries in device memory, uploaded once by the
+ * caller, as rd_pack_weights_batched's table_dev.  table_host is read for validation only; nothing on the device is dereferenced by
+ * the host.  Within a chunk the part where source and destination are both 16-byte aligned moves with 16-byte loads and stores, the
+ * words in front of and behind it (or the whole chunk, when the two sides are aligned differently) with 4-byte accesses.
+ * At most two launches on `stream`, both kernels through the library's one launch site: a clear of the 2 n sums, then the copy (none
+ * at all for n == 0, which succeeds; the clear alone when every range is empty).  No hipMemcpyAsync / hipMemsetAsync; allocates
+ * nothing, synchronises nothing; the caller owns every buffer.  Returns, before anything is launched: -1 n < 0 (or > 2^24) or a null
+ * table / staging / sums, -2 a byte count that is negative or not a multiple of 4, -3 a misaligned range start, offset, staging or
+ * sums pointer (or a null start with bytes > 0), -4 offsets that overlap, descend or leave staging_bytes, -5 a chunk0 column or
+ * total_chunks that does not match the byte counts, -6 a direction other than 0 or 1. */
+#define RD_SNAP_CHUNK 65536
+#define RD_SNAP_SUM_STRIDE 16
+typedef struct {
+    void* ptr;                  /* device start of the range */
+    int64_t bytes;
+    int64_t offset;             /* byte offset in the staging buffer */
+    int64_t chunk0;             /* first chunk of the range in the flat grid */
+} rd_snap_range_t;
+int rd_snapshot(const rd_snap_range_t* table_host, const rd_snap_range_t* table_dev, int n, int64_t total_chunks, void* staging,
+                int64_t staging_bytes, uint64_t* sums_dev, int direction, void* stream);
+
 /* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
  * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
  * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */

@@ -148,6 +148,14 @@ class RdStepLog(C.Structure):
                 ('n_rec', i32), ('pad_', i32), ('partial', vp)]
 
 
+SNAP_CHUNK, SNAP_SUM_STRIDE = 65536, 16                             # RD_SNAP_CHUNK, RD_SNAP_SUM_STRIDE (64-bit words)
+
+
+class RdSnapRange(C.Structure):
+    """rd_snap_range_t (include/ramdsir.h): one range of rd_snapshot's table."""
+    _fields_ = [('ptr', vp), ('bytes', i64), ('offset', i64), ('chunk0', i64)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -231,7 +239,8 @@ _SIGS = {
     'rd_tb_grids': (C.c_int, [C.POINTER(RdTbGrid), C.c_int, vp, i64, vp]),
     'rd_step_log': (C.c_int, [C.POINTER(RdStepLog), vp]),
     'rd_step_log_workspace': (i64, [i64]),
-    'rd_crc32c': (C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
+    'rd_snapshot': (C.c_int, [C.POINTER(RdSnapRange), vp, C.c_int, i64, vp, i64, vp, C.c_int, vp]),
+    'rd_crc32c':(C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),
     'rd_prostate_batch': (C.c_int, [C.POINTER(RdProstateBatch), C.POINTER(RdProstateSample), C.c_int, vp]),

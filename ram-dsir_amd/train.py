@@ -14,7 +14,10 @@ reference's tags, to a TensorBoard event file in <save_path>/log (utils/tfevents
 (ramdsir/step_log.py), and --tb_health adds per-iteration gradient norms and a non-finite count through the same ring;
 (iii) multi-GPU is one process per GPU with an RCCL gradient all-reduce instead of nn.DataParallel; (iv) the tensorboard image
 grids (train.py:306-329, 475-496) are opt-in (--tb_images: composed on the GPU, ramdsir/tb_images.py) and the source-tree snapshot
-(train.py:534-536) is not reproduced.
+(train.py:534-536) is not reproduced; (v) --ckpt_every N snapshots the whole training state (model, Adam moments, BatchNorm buffers,
+schedule counter, host generators, the cycled loaders' replay lists) every N epochs through one HIP gather and a writer thread, --resume
+continues from such a file -- bit-identically with --gpu_data or --num_workers 0 -- and --stop_after_epochs slices a run into jobs
+(ramdsir/ckpt.py); the reference can only start from a fresh initialisation.
 """
 import argparse
 import os
@@ -111,6 +114,17 @@ def parse_args(argv=None):
                    help='per iteration, through the same ring: the gradient norm of each Adam group (health/grad_norm_encoder, _seg_decoder, '
                         '_rec_decoder) and the number of non-finite gradient elements (health/nonfinite_grads); one console line names the '
                         'first iteration with non-finite losses or gradients; --norm bn only; off by default')
+    p.add_argument('--ckpt_every', type=int, default=0, metavar='N',
+                   help='every N epochs, after the validation and the keep-best rotation, snapshot the WHOLE training state (parameters, Adam '
+                        'moments, BatchNorm buffers, the schedule counter, the host generators, the replay lists of the cycled loaders) to '
+                        '<save_path>/last_state.pth: one HIP gather (ramdsir/ckpt.py, rd_snapshot), a copy beside the next epoch, a writer '
+                        'thread; --norm bn, one process; 0 = off (the default)')
+    p.add_argument('--resume', type=str, default=None, metavar='PATH',
+                   help='continue from a --ckpt_every snapshot: with --gpu_data or --num_workers 0 the continuation is bit-identical to the '
+                        'uninterrupted run; the arguments that shape the run must be those of the snapshot')
+    p.add_argument('--stop_after_epochs', type=int, default=0, metavar='K',
+                   help='leave after K epochs of THIS process, once the last snapshot is on disk, without writing final_model.pth -- as a '
+                        'preempted job would; needs --ckpt_every (slices a run into jobs)')
     return p.parse_args(argv)
 
 
@@ -264,9 +278,10 @@ def save_checkpoint(path, encoder, seg_decoder, rec_decoder):
                 'rec_decoder_state_dict': rec_decoder.state_dict()}, path)
 
 
-def make_loaders(args, data_root, world, rank, bsl, domain_idx_list):
+def make_loaders(args, data_root, world, rank, bsl, domain_idx_list, replay=False):
     """train.py:554-560: one loader per training domain, cycled except the longest.  --gpu_data: the same construction over the
-    parameter datasets of ramdsir/gpu_data.py, loaded in this process.  Returns (raw loaders, samplers, iterables, longest length)."""
+    parameter datasets of ramdsir/gpu_data.py, loaded in this process.  replay (--ckpt_every / --resume): the cycles are ckpt.ReplayCycle,
+    itertools.cycle with a state that can be saved.  Returns (raw loaders, samplers, iterables, longest length)."""
     zoo = {'fundus': Fundus_Multi, 'prostate': Prostate_Multi}
     if args.gpu_data:
         from ramdsir import gpu_data
@@ -294,7 +309,11 @@ def make_loaders(args, data_root, world, rank, bsl, domain_idx_list):
                         worker_init_fn=seed_worker, **extra)
         raw.append(dl)
         samplers.append(sampler)
-        loaders.append(cycle(dl))                       # train.py:560: replays the first pass of the shorter loaders
+        if replay:
+            from ramdsir.ckpt import ReplayCycle
+            loaders.append(ReplayCycle(dl))
+        else:
+            loaders.append(cycle(dl))                   # train.py:560: replays the first pass of the shorter loaders
         if max_len < len(dl):
             max_len, max_id = len(dl), idx
     loaders[max_id] = raw[max_id]
@@ -304,6 +323,15 @@ def make_loaders(args, data_root, world, rank, bsl, domain_idx_list):
 def uses_step_log(args):
     """Either flag turns the per-step ring on (ramdsir/step_log.py); without both, the run never touches it."""
     return bool(args.tb_every_iter or args.tb_health)
+
+
+def uses_ckpt(args):
+    """Any of the three flags turns the resumable-state machinery on (ramdsir/ckpt.py); without them the run never touches it."""
+    return bool(args.ckpt_every or args.resume or args.stop_after_epochs)
+
+
+def val_log_path(args):
+    return osp.join(args.save_path, str(args.test_domain_idx) + '_val_log.csv')
 
 
 def console_line(iter_num, lr_now, l):
@@ -350,8 +378,23 @@ def main(args):
                          'losses are host-visible tensors (use --log_every 1 there)' % args.norm)
     if args.fused_val and args.norm != 'bn':
         raise ValueError('--fused_val freezes BatchNorm on its running statistics: --norm %s has none (validate through the modules)' % args.norm)
+    ckpt_on = uses_ckpt(args)
+    if args.ckpt_every < 0 or args.stop_after_epochs < 0:
+        raise ValueError('--ckpt_every / --stop_after_epochs take a number of epochs, got %d / %d' % (args.ckpt_every, args.stop_after_epochs))
+    if args.stop_after_epochs and not args.ckpt_every:
+        raise ValueError('--stop_after_epochs leaves the run to be resumed: it needs --ckpt_every')
+    if ckpt_on and args.norm != 'bn':
+        raise ValueError('--ckpt_every / --resume / --stop_after_epochs snapshot the fused step\'s arenas: --norm %s trains through the modules, '
+                         'whose Adam is torch\'s' % args.norm)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    if ckpt_on and world > 1:
+        raise ValueError('--ckpt_every / --resume / --stop_after_epochs run in one process: BatchNorm buffers, generators and replay lists '
+                         'are rank-local (WORLD_SIZE=%d)' % world)
+    resume_state = None
+    if args.resume:
+        from ramdsir import ckpt
+        resume_state = ckpt.load_file(args.resume)          # an unknown format version or a corrupt range is refused here
     local = int(os.environ.get('LOCAL_RANK', '0'))
     data_root = os.path.join(args.data_root, args.dataset)
     # The validation pool (fork) and the persistent test loader -- with its worker processes started (_val_resources) -- are created
@@ -380,7 +423,7 @@ def main(args):
 
     bsl = fundus_batch_list[args.test_domain_idx] if args.dataset == 'fundus' else prostate_batch_list[args.test_domain_idx]
     domain_idx_list = [int(i) for i in args.domain_idxs.split(',')]
-    raw, samplers, loaders, max_len = make_loaders(args, data_root, world, rank, bsl, domain_idx_list)
+    raw, samplers, loaders, max_len = make_loaders(args, data_root, world, rank, bsl, domain_idx_list, replay=ckpt_on)
     resident = None
     if args.gpu_data:
         # decode once, keep the pixels on this GPU (ramdsir/gpu_data.py); the loaders above only draw
@@ -455,6 +498,18 @@ def main(args):
                            consistency=cons, lambda_rec=args.lambda_rec, lr=args.lr, total_iters=total_iters,
                            dtype=torch.bfloat16 if (args.dtype or ('bf16' if args.norm == 'bn' else 'f32')) == 'bf16' else torch.float32)
 
+    state_io = None
+    if ckpt_on:
+        # the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py); --resume: the arenas, the BatchNorm
+        # buffers and the schedule counter from the file (the host side follows immediately before the epoch loop)
+        from ramdsir import ckpt
+        state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, bsl[:len(domain_idx_list)], domain_idx_list, H, W, total_iters))
+        if resume_state is not None:
+            state_io.restore(resume_state)
+        if not args.gpu_data and args.num_workers > 0:
+            print('ckpt: model, optimizer and schedule state are restored exactly; with DataLoader worker processes the draws come from '
+                  'freshly seeded workers (use --gpu_data or --num_workers 0 for a bit-identical continuation)')
+
     if rank == 0 and args.fused_val:
         # the validation forward pass as one launch list over the trainer's own parameter arena (ramdsir/infer.py); only where the
         # resident validation is in use (a test set that did not fit validates on the host, through the modules)
@@ -496,7 +551,26 @@ def main(args):
 
     previous_best, iter_num = 0.0, 0
     t_mark, it_mark, imgs_per_iter = None, 0, world * sum(bsl[:len(domain_idx_list)])
-    for epoch in range(args.epochs):
+    start_epoch, epochs_here, stopped = 0, 0, False
+    if resume_state is not None:
+        # the host side of the snapshot, behind every start-up draw (the loaders' construction, next(iter(raw[0])), the --gpu_val draw):
+        # the three generators and the cycles as the snapshotted process left them at the end of its epoch
+        meta = resume_state['meta']
+        ckpt.set_host_rng_state(meta['rng'])
+        for idx, st in enumerate(meta['cycles']):
+            if (st is None) != (loaders[idx] is raw[idx]):
+                raise ValueError('--resume: the snapshot cycles other loaders than this run (domain %d)' % idx)
+            if st is not None:
+                loaders[idx] = ckpt.ReplayCycle.from_state(st)
+        start_epoch, iter_num, previous_best = meta['epoch'] + 1, meta['iter_num'], meta['previous_best']
+        if os.path.exists(val_log_path(args)) and os.path.getsize(val_log_path(args)) > meta['val_log_bytes']:
+            print('resume: %s truncated from %d to %d bytes (lines of epochs that ran after the snapshot and run again)'
+                  % (val_log_path(args), os.path.getsize(val_log_path(args)), meta['val_log_bytes']))
+            with open(val_log_path(args), 'r+b') as f:
+                f.truncate(meta['val_log_bytes'])
+        print('resume: %s, continuing at epoch %d (iteration %d, best %.2f)' % (args.resume, start_epoch, iter_num, previous_best))
+        resume_state = meta = None
+    for epoch in range(start_epoch, args.epochs):
         it_epoch = iter_num
         if rank == 0:
             print('\n==> Epoch %i, learning rate = %.6f' % (epoch, args.lr if iter_num == 0 else trainer.lr()))
@@ -583,15 +657,31 @@ def main(args):
                     os.remove(old)
             save_checkpoint(os.path.join(args.save_path, 'model_%.2f.pth' % avg_dice), encoder, seg_decoder, rec_decoder)
             previous_best = avg_dice
+        if state_io is not None and args.ckpt_every and (epoch + 1) % args.ckpt_every == 0:
+            state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), dict(
+                epoch=epoch, iter_num=iter_num, previous_best=previous_best, rng=ckpt.host_rng_state(),
+                cycles=[None if it is dl else it.state() for it, dl in zip(loaders, raw)],
+                val_log_bytes=os.path.getsize(val_log_path(args)) if os.path.exists(val_log_path(args)) else 0))
         if rank == 0:
             t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * imgs_per_iter
             print('epoch %d: training %.2f s (%.0f images/s), validation + checkpoint %.2f s (%.0f images/s over the whole epoch)'
                   % (epoch, t_train, n_img / max(t_train, 1e-9), t_all - t_train, n_img / max(t_all, 1e-9)))
         if args.max_iters and iter_num >= args.max_iters:
             break
+        epochs_here += 1
+        if args.stop_after_epochs and epochs_here >= args.stop_after_epochs and epoch + 1 < args.epochs:
+            stopped = True                              # --stop_after_epochs: as a preempted job, no final_model.pth
+            break
     if step_log:
         write_step_log()                                # the rows behind the last logging iteration
-    if rank == 0:
+    if state_io is not None:
+        state_io.close()                                # the last snapshot is durable
+        if state_io.seconds['calls']:
+            print(state_io.report())
+    if stopped:
+        print('\nStopped after %d epochs of this process (epoch %d of %d); resume from %s'
+              % (epochs_here, epoch, args.epochs, osp.join(args.save_path, 'last_state.pth')))
+    elif rank == 0:
         save_checkpoint(os.path.join(args.save_path, 'final_model.pth'), encoder, seg_decoder, rec_decoder)
         print('\nSave Final Model to {}'.format(args.save_path))
     if writer is not None:

@@ -3,11 +3,12 @@
 (the size of the reference's ROIs) + gray masks in the reference's list layout, then the drop-in CLI with the reference's
 loader settings (train.py:558: batch [3,6,7] for target 0, num_workers=8 per domain loader, pin_memory, shuffle,
 Resize(256) + RandomScaleCrop(256)).  Prints train.py's `train throughput` line; compare with bench.py's resident-input
-number at --size 256.   python scripts/e2e_train_throughput.py [--n 48] [--iters 120] [--workers 8] [--gpu_data] [--gpu_val] [--n_test 8] [--tb_images N] [--tb_every_iter] [--tb_health] [--log_every N]
+number at --size 256.   python scripts/e2e_train_throughput.py [--n 48] [--iters 120] [--workers 8] [--gpu_data] [--gpu_val] [--n_test 8] [--tb_images N] [--tb_every_iter] [--tb_health] [--log_every N] [--ckpt_every N]
 --gpu_data: train.py's GPU-resident data path (decode once, one augmentation launch per step; --workers sizes the preload pool).
 --gpu_val: train.py's GPU validation path; --n_test: test images per domain (the real lists hold 51-80).
 --tb_images N: train.py's TensorBoard image grids every N iterations (also prints the writer thread's host time per logging iteration).
 --tb_every_iter / --tb_health: train.py's per-step record ring; --log_every N: how often train.py reads the losses back (default 50).
+--ckpt_every N: train.py's resumable-state snapshot every N epochs (also prints the writer thread's per-stage line).
 --tree DIR: build the tree in DIR, or use the one already there (several runs on the same files)."""
 import argparse
 import os
@@ -33,6 +34,7 @@ ap.add_argument('--tb_images', type=int, default=0)
 ap.add_argument('--tb_every_iter', action='store_true')
 ap.add_argument('--tb_health', action='store_true')
 ap.add_argument('--log_every', type=int, default=50)
+ap.add_argument('--ckpt_every', type=int, default=0)
 ap.add_argument('--tree', default=None)
 a = ap.parse_args()
 with tempfile.TemporaryDirectory() as out_tmp:
@@ -47,8 +49,9 @@ with tempfile.TemporaryDirectory() as out_tmp:
            '--dtype', a.dtype] + (['--gpu_data'] if a.gpu_data else []) + (['--gpu_val'] if a.gpu_val else []) + \
           (['--fused_val'] if a.fused_val else []) + \
           (['--tb_images', str(a.tb_images)] if a.tb_images else []) + \
-          (['--tb_every_iter'] if a.tb_every_iter else []) + (['--tb_health'] if a.tb_health else [])
+          (['--tb_every_iter'] if a.tb_every_iter else []) + (['--tb_health'] if a.tb_health else []) + \
+          (['--ckpt_every', str(a.ckpt_every)] if a.ckpt_every else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     out = r.stdout.decode()
-    print('\n'.join(l for l in out.splitlines() if 'throughput' in l or 'epoch ' in l or 'gpu_data:' in l or 'gpu_val:' in l or 'tb_images:' in l or 'Error' in l or 'error' in l)[-3000:])
+    print('\n'.join(l for l in out.splitlines() if 'throughput' in l or 'epoch ' in l or 'gpu_data:' in l or 'gpu_val:' in l or 'tb_images:' in l or l.startswith('ckpt:') or 'Error' in l or 'error' in l)[-3000:])
     sys.exit(r.returncode)
