@@ -319,3 +319,9 @@ def gstart_array(gs):
 
 def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    """torch's current stream as the c_void_p that every entry point declares for its trailing stream argument."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -22,6 +22,7 @@ from PIL import Image
 from torch.utils.data import Dataset
 
 from ramdsir import _lib as L, resample as RS
+from ramdsir._lib import _stream
 
 FUNDUS_DOMAINS = ['Domain1', 'Domain2', 'Domain3', 'Domain4']            # dataset/fundus.py DOMAINS
 PROSTATE_DOMAINS = ['Domain1', 'Domain2', 'Domain3', 'Domain4', 'Domain5', 'Domain6']
@@ -137,10 +138,6 @@ def _check_memory(nbytes, device, what):
     if nbytes > MEM_SHARE * free:
         raise RuntimeError('--gpu_data: the resident %s data takes %.2f GB, more than %d %% of the %.2f GB free on %s; train without '
                            '--gpu_data' % (what, nbytes / 1e9, int(MEM_SHARE * 100), free / 1e9, device))
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _rgb_size(path):

@@ -11,7 +11,6 @@ give equal numbers.
 `postprocess_model` and `resize_threshold_model` state the kernels' rules in plain numpy: they are what the kernels are read
 against, and the CPU suite pins them to scipy and to F.interpolate.
 """
-import ctypes as C
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -20,6 +19,7 @@ import torch
 from PIL import Image
 
 from ramdsir import _lib as L
+from ramdsir._lib import _stream
 
 MEM_SHARE = 0.5             # as ramdsir/gpu_data.py: at most this share of the device memory free at preload
 THRESHOLD = 0.75
@@ -158,10 +158,6 @@ def dice_from_counts(n_post, n_gt, n_inter):
 
 # ----------------------------------------------------------------------------------------------------------------------------------
 # device side
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def image_records(sizes, gt_offs=None, slots=None):
     """rd_val_image_t records of images stored back to back in list order: ((h, w), ...) -> (ctypes array, bytes of the buffer)."""
     arr = (L.RdValImage * max(len(sizes), 1))()
@@ -293,48 +289,32 @@ def validate(encoder, seg_decoder, res, batch_size=8, keep=None, forward=None):
     """One validation pass over the resident set: the forward pass of train.py::test_fundus on batches of `batch_size` in list order,
     stages a-c per batch, one device-to-host copy.  Returns [(cup dice, disc dice)] per image.  keep: a list that receives
     (thresholded masks, post-processed masks, records) of every batch (tests).  forward: an infer.EvalForward over the same
-    parameters (--fused_val): the forward pass is its launch list instead of the modules, the same masks and counts."""
-    if forward is not None:
-        return _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep)
-    n = len(res)
-    counts = torch.zeros((max(n, 1), 2, 3), dtype=torch.int32, device=res.inputs.device)
-    encoder.eval()
-    seg_decoder.eval()
-    with torch.no_grad():
-        for b0 in range(0, n, batch_size):
-            b1 = min(b0 + batch_size, n)
-            logits = seg_decoder(encoder(res.inputs[b0:b1]))
-            recs, nbytes = image_records(res.sizes[b0:b1], res.gt_offs[b0:b1], range(b0, b1))
-            mask = threshold(logits, recs, b1 - b0, nbytes)
-            out = post(mask, recs, b1 - b0, nbytes, res.gt, counts)
-            if keep is not None:
-                keep.append((mask, out, recs))
-    c = counts.cpu().tolist()                               # the pass's only synchronisation
-    return [(dice_from_counts(*c[i][0]), dice_from_counts(*c[i][1])) for i in range(n)]
-
-
-def _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep):
-    """validate() with the forward pass as EvalForward's launch list: refresh() once, then per batch the resident NHWC slice is copied
-    into the plan's input, ONE rd_run_list call, and stage a reads the plan's logits in place (rd_val_threshold_nhwc).  Stages b and c,
-    the counts and the copy that ends the pass are validate()'s."""
+    parameters (--fused_val): refresh() once, then per batch the resident NHWC slice is copied into the plan's input, ONE rd_run_list
+    call, and stage a reads the plan's logits in place (rd_val_threshold_nhwc) -- the same masks and counts as through the modules."""
     n = len(res)
     S, S2 = res.inputs.shape[2:4]
-    x0 = forward.input(min(batch_size, max(n, 1)), S, S2)
-    if res.inputs_nhwc is None or res.inputs_nhwc.dtype != x0.dtype or res.inputs_nhwc.shape[3] != x0.shape[3]:
-        res.keep_nhwc(x0.dtype, x0.shape[3])                # (a resident set preloaded without nhwc_dtype, or for another layout)
+    if forward is not None:
+        x0 = forward.input(min(batch_size, max(n, 1)), S, S2)
+        if res.inputs_nhwc is None or res.inputs_nhwc.dtype != x0.dtype or res.inputs_nhwc.shape[3] != x0.shape[3]:
+            res.keep_nhwc(x0.dtype, x0.shape[3])            # (a resident set preloaded without nhwc_dtype, or for another layout)
     counts = torch.zeros((max(n, 1), 2, 3), dtype=torch.int32, device=res.inputs.device)
-    encoder.eval()                                          # the flags the module path leaves behind
+    encoder.eval()                                          # fused too: the flags the module path leaves behind
     seg_decoder.eval()
     with torch.no_grad():
-        forward.refresh()
+        if forward is not None:
+            forward.refresh()
         for b0 in range(0, n, batch_size):
             b1 = min(b0 + batch_size, n)
-            forward.input(b1 - b0, S, S2).copy_(res.inputs_nhwc[b0:b1])
-            logits = forward.run(b1 - b0, S, S2)
             recs, nbytes = image_records(res.sizes[b0:b1], res.gt_offs[b0:b1], range(b0, b1))
-            mask = threshold_nhwc(logits, recs, b1 - b0, nbytes)
+            if forward is None:                             # the forward pass and stage a: all that the two modes do not share
+                mask = threshold(seg_decoder(encoder(res.inputs[b0:b1])), recs, b1 - b0, nbytes)
+            else:
+                forward.input(b1 - b0, S, S2).copy_(res.inputs_nhwc[b0:b1])
+                mask = threshold_nhwc(forward.run(b1 - b0, S, S2), recs, b1 - b0, nbytes)
             out = post(mask, recs, b1 - b0, nbytes, res.gt, counts)
             if keep is not None:
                 keep.append((mask, out, recs))
     c = counts.cpu().tolist()                               # the pass's only synchronisation
     return [(dice_from_counts(*c[i][0]), dice_from_counts(*c[i][1])) for i in range(n)]
+
+

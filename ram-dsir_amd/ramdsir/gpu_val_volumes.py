@@ -11,13 +11,13 @@ Dice doubles are then evaluated on the host from integers with metrics.dc's form
 `stack_model`, `argmax_model` and `largest_component_model` state the kernels' rules in plain numpy: they are what the kernels are
 read against, and the CPU suite pins them to predict_volume and to scipy.
 """
-import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from ramdsir import _lib as L
+from ramdsir._lib import _stream
 from ramdsir.gpu_val import _run_index, _runs
 
 MEM_SHARE = 0.5             # as ramdsir/gpu_val.py: at most this share of the device memory free at preload
@@ -123,10 +123,6 @@ def dice_from_counts(n_post, n_gt, n_inter):
 
 # ----------------------------------------------------------------------------------------------------------------------------------
 # device side
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _frames(frames):
     return (L.i32 * len(frames))(*[int(f) for f in frames])
 
@@ -291,21 +287,24 @@ def validate(encoder, seg_decoder, res, batch_size=8, keep=None, forward=None):
     """One validation pass over the resident volumes: per volume the batches of predict_volume through the modules (eval mode,
     no_grad), then the post-processing of all volumes, one device-to-host copy.  Returns the Dice of every volume in list order.
     keep: a dict that receives the prediction and the post-processed volumes as numpy arrays (tests).  forward: an
-    infer.EvalForward over the same parameters (--fused_val): the forward pass is its launch list instead of the modules, the same
-    volumes and counts."""
-    if forward is not None:
-        return _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep)
+    infer.EvalForward over the same parameters (--fused_val): refresh() once, then per batch rd_vol_stack_nhwc writes the plan's
+    input, ONE rd_run_list call, rd_vol_argmax_nhwc reads the plan's logits in place -- the same volumes and counts."""
     n = len(res)
     counts = torch.zeros((max(n, 1), 3), dtype=torch.int32, device=res.gt.device)
-    encoder.eval()
+    encoder.eval()                                          # fused too: the flags the module path leaves behind
     seg_decoder.eval()
     with torch.no_grad():
+        if forward is not None:
+            forward.refresh()
         zero(res.pred)                                      # slices that no batch reaches, and empty slots, stay zero
         for i in range(n):
-            pred = res.pred[res.offs[i]:res.offs[i + 1]]
+            pred, (_, H, W) = res.pred[res.offs[i]:res.offs[i + 1]], res.shapes[i]
             for frames in frame_batches(res.shapes[i][0], batch_size):
-                logits = seg_decoder(encoder(stack(res.volumes[i], frames)))
-                argmax(logits, frames, res.gt_empty[i], pred, res.shapes[i])
+                if forward is None:                         # the batch's forward pass: all that the two modes do not share
+                    argmax(seg_decoder(encoder(stack(res.volumes[i], frames))), frames, res.gt_empty[i], pred, res.shapes[i])
+                else:
+                    stack_nhwc(res.volumes[i], frames, forward.input(len(frames), H, W))
+                    argmax_nhwc(forward.run(len(frames), H, W), frames, res.gt_empty[i], pred, res.shapes[i])
         groups = [(volume_records(res.shapes[a:b], res.offs[a:b], slots=range(a, b))[0], b - a) for a, b in post_groups(res.shapes)]
         ws_bytes = max([L.lib().rd_vol_post_workspace(recs, m) for recs, m in groups] or [0])
         workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=res.gt.device)
@@ -319,30 +318,3 @@ def validate(encoder, seg_decoder, res, batch_size=8, keep=None, forward=None):
     return [dice_from_counts(*c[i]) for i in range(n)]
 
 
-def _validate_fused(forward, encoder, seg_decoder, res, batch_size, keep):
-    """validate() with the forward pass as EvalForward's launch list: refresh() once, then per batch rd_vol_stack_nhwc writes the plan's
-    input, ONE rd_run_list call, rd_vol_argmax_nhwc reads the plan's logits in place.  The rest is validate()'s."""
-    n = len(res)
-    counts = torch.zeros((max(n, 1), 3), dtype=torch.int32, device=res.gt.device)
-    encoder.eval()                                          # the flags the module path leaves behind
-    seg_decoder.eval()
-    with torch.no_grad():
-        forward.refresh()
-        zero(res.pred)                                      # slices that no batch reaches, and empty slots, stay zero
-        for i in range(n):
-            pred = res.pred[res.offs[i]:res.offs[i + 1]]
-            _, H, W = res.shapes[i]
-            for frames in frame_batches(res.shapes[i][0], batch_size):
-                stack_nhwc(res.volumes[i], frames, forward.input(len(frames), H, W))
-                argmax_nhwc(forward.run(len(frames), H, W), frames, res.gt_empty[i], pred, res.shapes[i])
-        groups = [(volume_records(res.shapes[a:b], res.offs[a:b], slots=range(a, b))[0], b - a) for a, b in post_groups(res.shapes)]
-        ws_bytes = max([L.lib().rd_vol_post_workspace(recs, m) for recs, m in groups] or [0])
-        workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=res.gt.device)
-        for recs, m in groups:
-            post(res.pred, res.post, recs, m, res.gt, counts, workspace)
-    c = counts.cpu().tolist()                               # the pass's only synchronisation
-    if keep is not None:
-        keep['pred'] = [res.pred[res.offs[i]:res.offs[i + 1]].cpu().numpy().reshape(res.shapes[i]) for i in range(n)]
-        keep['post'] = [res.post[res.offs[i]:res.offs[i + 1]].cpu().numpy().reshape(res.shapes[i]) for i in range(n)]
-        keep['counts'] = c
-    return [dice_from_counts(*c[i]) for i in range(n)]

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._lib import _stream
 from . import engine as E
 from . import modules as M
 
@@ -53,10 +54,6 @@ def site_table(sites):
         arr[i].gamma, arr[i].beta, arr[i].running_mean, arr[i].running_var = g.data_ptr(), b.data_ptr(), rm.data_ptr(), rv.data_ptr()
         arr[i].scale, arr[i].shift, arr[i].C = sc.data_ptr(), sh.data_ptr(), int(Cc)
     return arr
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class _Bound:

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._lib import _stream
 from . import engine as E
 
 
@@ -232,10 +233,6 @@ class FusedModule(nn.Module):
 
     def _param_list(self):
         return [p for _, p in self.named_parameters()]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def to_nhwc(x, act_buf, dt):

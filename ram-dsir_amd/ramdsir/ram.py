@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._lib import _stream
 from . import engine as E
 
 
@@ -133,10 +134,6 @@ def _dev():
     if not torch.cuda.is_available():
         raise RuntimeError('the RAM kernels need a GPU: there is no CPU fallback')
     return torch.device('cuda', torch.cuda.current_device())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def extract_amp_spectrum_gpu(img_chw):

@@ -296,9 +296,7 @@ class TrainStep:
     def load_target(self, mask):
         self.target.copy_(mask)
 
-    @staticmethod
-    def _stream():
-        return torch.cuda.current_stream().cuda_stream
+    _stream = staticmethod(L._stream)
 
     # ---- execution
     def zero(self, stream=None):

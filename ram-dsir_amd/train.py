@@ -143,46 +143,60 @@ def seed_worker(worker_id):
     random.seed(worker_seed)
 
 
-_VAL = {}
+def fundus_testset(data_dir, datasetTest):
+    return Fundus(base_dir=data_dir, split='test', domain_idx=datasetTest, transform=Compose([trans.Resize((256, 256)), trans.Normalize()]))
 
 
-def _val_resources(data_dir, datasetTest, batch_size):
-    """The test loader and the post-processing pool live across epochs: the reference rebuilds an 8-worker loader and
-    post-processes every 800x800 prediction serially at every epoch (~0.2 s per image: connected components + hole filling) --
-    seconds per epoch, invisible next to its training time, most of the wall clock next to this one's."""
-    key = (data_dir, datasetTest, batch_size)
-    if key not in _VAL:
-        import multiprocessing as mp
-        testset = Fundus(base_dir=data_dir, split='test', domain_idx=datasetTest,
-                         transform=Compose([trans.Resize((256, 256)), trans.Normalize()]))
-        nw = min(8, max(1, len(testset) // 2))
-        loader = DataLoader(testset, batch_size=batch_size, num_workers=nw, shuffle=False, drop_last=False, pin_memory=True,
-                            persistent_workers=True)
-        pool = mp.get_context('fork').Pool(min(16, max(2, (os.cpu_count() or 4) // 4)))     # children never touch the GPU
-        # a DataLoader forks its workers at the first iter(), not at construction: start them NOW (main() calls this before the
-        # first GPU call), so that they too are forked from an address space that has never initialised HIP.  With
-        # persistent_workers the DataLoader keeps this iterator (and its workers) and resets it at every later `for ... in loader`.
-        it = iter(loader)
-        _VAL[key] = (loader, pool, it)
-    return _VAL[key][:2]
+def start_host_val(data_dir, datasetTest, batch_size):
+    """The test loader and the post-processing pool of the Fundus host path, made to live across epochs: the reference rebuilds an
+    8-worker loader and post-processes every 800x800 prediction serially at every epoch (~0.2 s per image: connected components +
+    hole filling) -- seconds per epoch, invisible next to its training time, most of the wall clock next to this one's.
+    Call it BEFORE the process's first GPU call.  Returns (loader, pool, the loader's started iterator) for close_host_val."""
+    import multiprocessing as mp
+    testset = fundus_testset(data_dir, datasetTest)
+    nw = min(8, max(1, len(testset) // 2))
+    loader = DataLoader(testset, batch_size=batch_size, num_workers=nw, shuffle=False, drop_last=False, pin_memory=True,
+                        persistent_workers=True)
+    pool = mp.get_context('fork').Pool(min(16, max(2, (os.cpu_count() or 4) // 4)))     # children never touch the GPU
+    # a DataLoader forks its workers at the first iter(), not at construction: start them NOW, from an address space that has never
+    # initialised HIP.  With persistent_workers it keeps this iterator (and its workers) and resets it at every `for ... in loader`.
+    return loader, pool, iter(loader)
 
 
-def _close_val():
-    for loader, pool, it in _VAL.values():
-        pool.terminate()
-        pool.join()
-        del it, loader                                      # persistent workers shut down with the loader's iterator
-    _VAL.clear()
+def close_host_val(host):
+    """Ends the pool; the loader's persistent workers shut down with its iterator, when the caller drops `host`."""
+    host[1].terminate()
+    host[1].join()
 
 
-def test_fundus(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='fundus'):
+def report_fundus(dices, epoch, datasetTest, output_path, batch_size):
+    """The end of train.py:91-132: the mean cup / disc Dice of [(cup, disc)] per image, the console line, the reference's CSV line."""
+    cup = disc = 0.0
+    for c, d in dices:
+        cup, disc = cup + c, disc + d
+    cup, disc = cup / max(len(dices), 1), disc / max(len(dices), 1)
+    print('val_cup_dice : {}, val_disc_dice : {}'.format(cup, disc))
+    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
+        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['cup dice coefficence: '] + [cup] +
+                                   ['disc dice coefficence: '] + [disc]])) + '\n')
+    return (cup + disc) * 100.0 / 2
+
+
+def report_prostate(val_dice, epoch, datasetTest, output_path, batch_size):
+    """The end of train.py:134-192: the console line and the reference's CSV line of the mean volume Dice."""
+    print('val_dice : {}'.format(val_dice))
+    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
+        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['dice coefficence: '] + [val_dice]])) + '\n')
+    return val_dice * 100.0
+
+
+def test_fundus(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='fundus', host=None):
     """train.py:91-132 (BN in eval mode here, as in the reference's in-training evaluation): sigmoid, bilinear resize to the
-    native mask size, threshold 0.75, largest component + hole filling, Dice with +1 smoothing, one CSV line."""
+    native mask size, threshold 0.75, largest component + hole filling, Dice with +1 smoothing, one CSV line.  host: what
+    start_host_val returned before the first GPU call; without it a loader and a pool live for this call, as in the reference."""
     encoder.eval()
     seg_decoder.eval()
-    loader, pool = _val_resources(data_dir, datasetTest, batch_size)
-    cup = disc = 0.0
-    n = 0
+    loader, pool, _ = own = host or start_host_val(data_dir, datasetTest, batch_size)
     pending = []
     with torch.no_grad():
         for data, target, target_orig, ids in loader:
@@ -191,46 +205,19 @@ def test_fundus(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path,
             masks = (pred > 0.75).to(torch.uint8).cpu().numpy()                  # the threshold of postprocessing(), on the GPU
             tg = target_orig.to(torch.uint8).numpy()
             pending.append(pool.map_async(post_and_dice, [(masks[i], tg[i]) for i in range(masks.shape[0])]))
-    for r in pending:
-        for c, d in r.get():
-            cup, disc, n = cup + c, disc + d, n + 1
-    cup, disc = cup / max(n, 1), disc / max(n, 1)
-    print('val_cup_dice : {}, val_disc_dice : {}'.format(cup, disc))
-    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
-        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['cup dice coefficence: '] + [cup] +
-                                   ['disc dice coefficence: '] + [disc]])) + '\n')
-    return (cup + disc) * 100.0 / 2
+    dices = [cd for r in pending for cd in r.get()]
+    if host is None:
+        close_host_val(own)
+    return report_fundus(dices, epoch, datasetTest, output_path, batch_size)
 
 
-def _val_testset(data_dir, datasetTest):
-    return Fundus(base_dir=data_dir, split='test', domain_idx=datasetTest, transform=Compose([trans.Resize((256, 256)), trans.Normalize()]))
-
-
-_VAL_GPU = {}
-
-
-def test_fundus_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='fundus', forward=None):
+def test_fundus_gpu(encoder, seg_decoder, epoch, resident, datasetTest, output_path, batch_size=8, forward=None):
     """test_fundus with everything after the forward pass on the GPU (--gpu_val; ramdsir/gpu_val.py, csrc/val_post.hip): the same
     batches in list order through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.
-    The resident test set is main()'s preload (or is made here at the first call).  forward (--fused_val): the infer.EvalForward that
-    runs the forward pass instead of the modules."""
+    resident: gpu_val.preload's set.  forward (--fused_val): the infer.EvalForward that runs the forward pass instead of the modules."""
     from ramdsir import gpu_val
-    key = (data_dir, datasetTest)
-    if key not in _VAL_GPU:
-        _VAL_GPU[key] = gpu_val.preload(_val_testset(data_dir, datasetTest), batch_size=batch_size)
-        if _VAL_GPU[key] is None:
-            raise RuntimeError('--gpu_val: the test set does not fit in device memory')
-    dices = gpu_val.validate(encoder, seg_decoder, _VAL_GPU[key], batch_size, forward=forward)
-    cup = disc = 0.0
-    n = 0
-    for c, d in dices:
-        cup, disc, n = cup + c, disc + d, n + 1
-    cup, disc = cup / max(n, 1), disc / max(n, 1)
-    print('val_cup_dice : {}, val_disc_dice : {}'.format(cup, disc))
-    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
-        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['cup dice coefficence: '] + [cup] +
-                                   ['disc dice coefficence: '] + [disc]])) + '\n')
-    return (cup + disc) * 100.0 / 2
+    return report_fundus(gpu_val.validate(encoder, seg_decoder, resident, batch_size, forward=forward), epoch, datasetTest, output_path,
+                         batch_size)
 
 
 def test_prostate(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='prostate'):
@@ -241,35 +228,117 @@ def test_prostate(encoder, seg_decoder, epoch, data_dir, datasetTest, output_pat
     seg_decoder.eval()
     with torch.no_grad():
         val_dice, _, _ = evaluate_domain(lambda v: seg_decoder(encoder(v.cuda())), data_dir, DOMAIN_LIST[datasetTest], batch_size)
-    print('val_dice : {}'.format(val_dice))
-    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
-        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['dice coefficence: '] + [val_dice]])) + '\n')
-    return val_dice * 100.0
+    return report_prostate(val_dice, epoch, datasetTest, output_path, batch_size)
 
 
-_VAL_VOL = {}
-
-
-def test_prostate_gpu(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='prostate', forward=None):
+def test_prostate_gpu(encoder, seg_decoder, epoch, resident, datasetTest, output_path, batch_size=8, forward=None):
     """test_prostate on the resident volumes (--gpu_val_volumes; ramdsir/gpu_val_volumes.py, csrc/val_volume.hip): the same batches
-    through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.  The resident
-    volumes are main()'s preload (or are made here at the first call).  forward (--fused_val): the infer.EvalForward that runs the
-    forward pass instead of the modules."""
+    through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.  resident:
+    gpu_val_volumes.preload's volumes.  forward (--fused_val): the infer.EvalForward that runs the forward pass instead of the modules."""
     from ramdsir import gpu_val_volumes
-    from utils.prostate_eval import DOMAIN_LIST
-    key = (data_dir, datasetTest)
-    if key not in _VAL_VOL:
-        _VAL_VOL[key] = gpu_val_volumes.preload(data_dir, DOMAIN_LIST[datasetTest], batch_size=batch_size)
-        if _VAL_VOL[key] is None:
-            raise RuntimeError('--gpu_val_volumes: the volumes do not fit in device memory')
     val_dice = 0.0
-    for d in gpu_val_volumes.validate(encoder, seg_decoder, _VAL_VOL[key], batch_size, forward=forward):
+    for d in gpu_val_volumes.validate(encoder, seg_decoder, resident, batch_size, forward=forward):
         val_dice += d
-    val_dice = val_dice / max(len(_VAL_VOL[key]), 1)
-    print('val_dice : {}'.format(val_dice))
-    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
-        f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['dice coefficence: '] + [val_dice]])) + '\n')
-    return val_dice * 100.0
+    return report_prostate(val_dice / max(len(resident), 1), epoch, datasetTest, output_path, batch_size)
+
+
+def val_mode(args, on_disk, fits=True):
+    """How this run validates, as data: (mode, console line at the resident preload or None, console line where the fused forward is
+    bound or None).  mode: 'none' (no data on disk), 'host', 'resident' (--gpu_val / --gpu_val_volumes) or 'fused' (resident with
+    --fused_val's forward).  on_disk: the held-out data exists; fits: the resident preload fitted (True before it has been tried)."""
+    wants_resident = args.gpu_val if args.dataset == 'fundus' else args.gpu_val_volumes and args.num_classes == 2
+    mode = 'none' if not on_disk else 'host' if not (wants_resident and fits) else 'fused' if args.fused_val else 'resident'
+    preload_line = bind_line = None
+    if args.dataset == 'prostate' and args.gpu_val_volumes and args.num_classes != 2:
+        # the host path sums the class indices of a component (ndi.sum(mask, ...)); the kernels count voxels: two classes only
+        preload_line = 'gpu_val_volumes: --num_classes %d is not 2: validating on the host' % args.num_classes
+    if args.fused_val and mode != 'fused':
+        bind_line = 'fused_val: the resident validation is not in use: validating through the modules'
+    return mode, preload_line, bind_line
+
+
+class Validation:
+    """The in-training validation of one run, on rank 0: the held-out domain, whether its data is on disk, and what the mode keeps
+    across epochs (the host path's loader and pool, or the resident data and --fused_val's forward).  Its three steps sit at fixed
+    places in main(): the constructor before the first GPU call, preload() on the device, bind() on the trainer."""
+
+    def __init__(self, args, data_root):
+        """INVARIANT: runs before the process's first HIP call.  Fundus host path: the pool and the test loader's workers are forked
+        here, and the loader's iterator takes one 64-bit draw (its base seed) from torch's global generator, which the training
+        samplers shuffle from.  --gpu_val creates neither and takes that one draw itself, so that the trained model does not depend
+        on the flag.  Prostate forks nothing and draws nothing."""
+        self.args, self.data_root, self.domain, self.batch_size = args, data_root, args.test_domain_idx, args.test_batch_size
+        self.fundus = args.dataset == 'fundus'
+        self.host = self.resident = self.forward = self.bind_line = None
+        if self.fundus:
+            self.on_disk = os.path.exists(os.path.join(data_root, 'Domain%d_test.list' % (self.domain + 1)))
+        else:
+            from utils.prostate_eval import DOMAIN_LIST
+            self.site = DOMAIN_LIST[self.domain]
+            self.on_disk = os.path.isdir(os.path.join(data_root, self.site))
+        self.mode = val_mode(args, self.on_disk)[0]         # 'resident' / 'fused' stand until preload() has tried
+        if self.fundus and self.mode == 'host':
+            self.host = start_host_val(data_root, self.domain, self.batch_size)
+        elif self.fundus and self.mode != 'none':
+            torch.empty((), dtype=torch.int64).random_()
+
+    def preload(self, workers):
+        """After torch.cuda.set_device: the held-out data, decoded once and kept on this GPU (ramdsir/gpu_val.py, gpu_val_volumes.py);
+        the host path if it does not fit.  INVARIANT: Fundus then starts the host resources late and leaves torch's generator where
+        it was (the constructor took the loader's draw); the Prostate host path has no loader and no pool, so nothing to reproduce."""
+        args, wants, t0 = self.args, self.mode in ('resident', 'fused'), time.time()
+        if wants and self.fundus:
+            from ramdsir import gpu_val, modules
+            nhwc = modules.storage_dtype() if args.fused_val else None      # the inputs also as the fused forward reads them
+            self.resident = val_set = gpu_val.preload(fundus_testset(self.data_root, self.domain), workers=workers,
+                                                      batch_size=self.batch_size, nhwc_dtype=nhwc)
+            if val_set is not None:
+                print('gpu_val: %d test images, %.3f GB resident%s, preloaded in %.1f s'
+                      % (len(val_set), val_set.nbytes / 1e9, '' if nhwc is None else ' (%.3f GB of it the NHWC %s inputs of --fused_val)'
+                         % (val_set.inputs_nhwc.numel() * val_set.inputs_nhwc.element_size() / 1e9, 'bf16' if nhwc == torch.bfloat16 else 'fp32'),
+                         time.time() - t0))
+            else:
+                rng_state = torch.get_rng_state()
+                self.host = start_host_val(self.data_root, self.domain, self.batch_size)
+                torch.set_rng_state(rng_state)
+        elif wants:
+            from ramdsir import gpu_val_volumes
+            self.resident = vols = gpu_val_volumes.preload(self.data_root, self.site, batch_size=self.batch_size, workers=workers)
+            if vols is not None:
+                print('gpu_val_volumes: %d volumes, %.3f GB resident + %.3f GB scratch, preloaded in %.1f s'
+                      % (len(vols), vols.nbytes / 1e9, vols.scratch_bytes / 1e9, time.time() - t0))
+        self.mode, line, self.bind_line = val_mode(args, self.on_disk, not wants or self.resident is not None)
+        if line:
+            print(line)
+
+    def bind(self, trainer):
+        """Once the trainer exists: --fused_val's forward pass as one launch list over the trainer's own parameter arena
+        (ramdsir/infer.py), only where the resident validation is in use (what did not fit validates through the modules)."""
+        if self.mode == 'fused':
+            from ramdsir.infer import EvalForward
+            self.forward = EvalForward.from_trainer(trainer)
+            print('fused_val: validation forward as one launch list per batch, %s storage, %s' % (
+                'bf16' if self.forward.dtype == torch.bfloat16 else 'fp32',
+                'its own weight pack (one repack per pass)' if self.forward.owns_pack else "the step's weight pack (no repack)"))
+        elif self.bind_line:
+            print(self.bind_line)
+
+    def __call__(self, encoder, seg_decoder, epoch):
+        """One pass (train.py:331-341): the average Dice in percent; None when the data is not on disk (synthetic / smoke runs)."""
+        if self.mode == 'none':
+            return None
+        print('Test on target domain {}'.format(self.domain))
+        models, tail = (encoder, seg_decoder, epoch), (self.domain, self.args.save_path, self.batch_size)
+        if self.mode == 'host' and self.fundus:
+            return test_fundus(*models, self.data_root, *tail, host=self.host)
+        if self.mode == 'host':
+            return test_prostate(*models, self.data_root, *tail)
+        return (test_fundus_gpu if self.fundus else test_prostate_gpu)(*models, self.resident, *tail, forward=self.forward)
+
+    def close(self):
+        if self.host is not None:
+            close_host_val(self.host)
+        self.host = self.resident = self.forward = None
 
 
 def save_checkpoint(path, encoder, seg_decoder, rec_decoder):
@@ -360,7 +429,8 @@ def record_is_finite(rec):
         and all(np.isfinite(v) for v in rec['norms'])
 
 
-def main(args):
+def check_args(args, world):
+    """Every flag combination this script refuses, and nothing else: no GPU call, no file, no process."""
     if not (args.ram and args.rec):
         # SURVEY.md F5: the reference only runs end-to-end with --ram --rec (train.py:591 / :315 raise otherwise)
         raise ValueError('only the --ram --rec flag combination exists in the reference; got ram=%s rec=%s' % (args.ram, args.rec))
@@ -372,113 +442,103 @@ def main(args):
         raise ValueError('--gpu_val_volumes covers the in-training Prostate validation only; --dataset %s has --gpu_val' % args.dataset)
     if args.fused_val and not (args.gpu_val or args.gpu_val_volumes):
         raise ValueError('--fused_val is the forward pass of the resident validation: it needs --gpu_val (fundus) or --gpu_val_volumes (prostate)')
-    step_log = uses_step_log(args)
-    if step_log and args.norm != 'bn':
+    if uses_step_log(args) and args.norm != 'bn':
         raise ValueError('--tb_every_iter / --tb_health read the fused step\'s device buffers: --norm %s trains through the modules, whose '
                          'losses are host-visible tensors (use --log_every 1 there)' % args.norm)
     if args.fused_val and args.norm != 'bn':
         raise ValueError('--fused_val freezes BatchNorm on its running statistics: --norm %s has none (validate through the modules)' % args.norm)
-    ckpt_on = uses_ckpt(args)
     if args.ckpt_every < 0 or args.stop_after_epochs < 0:
         raise ValueError('--ckpt_every / --stop_after_epochs take a number of epochs, got %d / %d' % (args.ckpt_every, args.stop_after_epochs))
     if args.stop_after_epochs and not args.ckpt_every:
         raise ValueError('--stop_after_epochs leaves the run to be resumed: it needs --ckpt_every')
-    if ckpt_on and args.norm != 'bn':
+    if uses_ckpt(args) and args.norm != 'bn':
         raise ValueError('--ckpt_every / --resume / --stop_after_epochs snapshot the fused step\'s arenas: --norm %s trains through the modules, '
                          'whose Adam is torch\'s' % args.norm)
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    if ckpt_on and world > 1:
+    if uses_ckpt(args) and world > 1:
         raise ValueError('--ckpt_every / --resume / --stop_after_epochs run in one process: BatchNorm buffers, generators and replay lists '
                          'are rank-local (WORLD_SIZE=%d)' % world)
-    resume_state = None
-    if args.resume:
-        from ramdsir import ckpt
-        resume_state = ckpt.load_file(args.resume)          # an unknown format version or a corrupt range is refused here
-    local = int(os.environ.get('LOCAL_RANK', '0'))
-    data_root = os.path.join(args.data_root, args.dataset)
-    # The validation pool (fork) and the persistent test loader -- with its worker processes started (_val_resources) -- are created
-    # HERE, before the first GPU call of this process: their children are forked from an address space that has never initialised
-    # HIP (rank 0 validates, below)
-    has_val = args.dataset == 'fundus' and os.path.exists(os.path.join(data_root, 'Domain%d_test.list' % (args.test_domain_idx + 1)))
-    if rank == 0 and has_val and args.gpu_val:
-        # The host path starts its test loader's iterator at this point (_val_resources), and a DataLoader iterator takes one 64-bit
-        # draw from torch's global generator for its base seed -- the generator the training samplers shuffle from.  --gpu_val creates
-        # neither the loader nor the pool; it takes that one draw here, so that the trained model does not depend on the flag.
-        torch.empty((), dtype=torch.int64).random_()
-    elif rank == 0 and has_val:
-        _val_resources(data_root, args.test_domain_idx, args.test_batch_size)
-    # DataLoader workers per domain loader: the reference's 8 (train.py:558) on one GPU; under torchrun every rank has its own
-    # three loaders, so the host's cores are divided among ranks x domains (8 ranks x 3 x 8 = 192 decoder processes otherwise)
-    n_dom = len(args.domain_idxs.split(','))
-    preload_workers = max(1, worker_cap(args.num_workers, world, 1))     # --gpu_data: threads decoding the resident data (<= 16)
-    args.num_workers = worker_cap(args.num_workers, world, n_dom)
-    torch.cuda.set_device(local)
-    if world > 1 and not dist.is_initialized():
-        dist.init_process_group('nccl', device_id=torch.device('cuda', local))
-    # host-side rendezvous (gloo) for the points where ranks wait for rank 0 on the CPU (validation): an RCCL barrier is a GPU
-    # kernel that spins until every peer has arrived
-    host_group = dist.new_group(backend='gloo') if world > 1 else None
-    os.makedirs(args.save_path, exist_ok=True)
 
-    bsl = fundus_batch_list[args.test_domain_idx] if args.dataset == 'fundus' else prostate_batch_list[args.test_domain_idx]
-    domain_idx_list = [int(i) for i in args.domain_idxs.split(',')]
-    raw, samplers, loaders, max_len = make_loaders(args, data_root, world, rank, bsl, domain_idx_list, replay=ckpt_on)
-    resident = None
-    if args.gpu_data:
-        # decode once, keep the pixels on this GPU (ramdsir/gpu_data.py); the loaders above only draw
-        from ramdsir import gpu_data
-        t0 = time.time()
-        resident = gpu_data.preload(args.dataset, [dl.dataset for dl in raw], workers=preload_workers)
-        if rank == 0:
-            print('gpu_data: %.2f GB resident, preloaded in %.1f s with %d threads' % (resident.nbytes / 1e9, time.time() - t0,
-                                                                                       preload_workers))
 
-    validate = test_fundus
-    if rank == 0 and has_val and args.gpu_val:
-        # the held-out test set, decoded once and kept on this GPU (ramdsir/gpu_val.py); the host path if it does not fit
-        from ramdsir import gpu_val
-        t0 = time.time()
-        nhwc = None
-        if args.fused_val:                                  # the inputs also in the layout and dtype the fused forward reads
-            from ramdsir import modules
-            nhwc = modules.storage_dtype()
-        val_set = gpu_val.preload(_val_testset(data_root, args.test_domain_idx), workers=preload_workers, batch_size=args.test_batch_size,
-                                  nhwc_dtype=nhwc)
-        if val_set is not None:
-            _VAL_GPU[(data_root, args.test_domain_idx)] = val_set
-            validate = test_fundus_gpu
-            print('gpu_val: %d test images, %.3f GB resident%s, preloaded in %.1f s'
-                  % (len(val_set), val_set.nbytes / 1e9, '' if nhwc is None else ' (%.3f GB of it the NHWC %s inputs of --fused_val)'
-                     % (val_set.inputs_nhwc.numel() * val_set.inputs_nhwc.element_size() / 1e9, 'bf16' if nhwc == torch.bfloat16 else 'fp32'),
-                     time.time() - t0))
-        else:
-            rng_state = torch.get_rng_state()               # the loader's draw has been taken above
-            _val_resources(data_root, args.test_domain_idx, args.test_batch_size)
-            torch.set_rng_state(rng_state)
+class TrainLog:
+    """The logging side of the loop: the event file in <save_path>/log (train.py:538) and the console lines of rank 0, and --
+    on every rank, because the drain is collective -- the reads of the per-step device ring (--tb_every_iter / --tb_health)."""
 
-    validate_prostate = test_prostate
-    if rank == 0 and args.gpu_val_volumes and args.num_classes != 2:
-        # the host path sums the class indices of a component (ndi.sum(mask, ...)); the kernels count voxels: two classes only
-        print('gpu_val_volumes: --num_classes %d is not 2: validating on the host' % args.num_classes)
-    elif rank == 0 and args.gpu_val_volumes:
-        # the held-out site's volumes, read once and kept on this GPU (ramdsir/gpu_val_volumes.py); the host path if they do not fit.
-        # The host path creates no loader for Prostate, so there is no random draw to reproduce here.
-        from ramdsir import gpu_val_volumes
-        from utils.prostate_eval import DOMAIN_LIST
-        if os.path.isdir(os.path.join(data_root, DOMAIN_LIST[args.test_domain_idx])):
-            t0 = time.time()
-            vols = gpu_val_volumes.preload(data_root, DOMAIN_LIST[args.test_domain_idx], batch_size=args.test_batch_size, workers=preload_workers)
-            if vols is not None:
-                _VAL_VOL[(data_root, args.test_domain_idx)] = vols
-                validate_prostate = test_prostate_gpu
-                print('gpu_val_volumes: %d volumes, %.3f GB resident + %.3f GB scratch, preloaded in %.1f s'
-                      % (len(vols), vols.nbytes / 1e9, vols.scratch_bytes / 1e9, time.time() - t0))
+    def __init__(self, args, trainer, rank, imgs_per_iter):
+        self.args, self.trainer, self.rank0, self.imgs_per_iter = args, trainer, rank == 0, imgs_per_iter
+        # --tb_images: one writer thread owns the event file (scalars go through its queue too, so the records keep the order of the
+        # calls); without the flag the direct writer, record for record what it always wrote
+        Writer = QueuedWriter if args.tb_images else SummaryWriter
+        self.writer = Writer(os.path.join(args.save_path, 'log')) if self.rank0 else None
+        self.first_bad = None                               # --tb_health: the first iteration with non-finite values, named once
+        self.t_mark, self.it_mark = None, 0                 # the throughput clock starts at iteration 5
+        self.step_log = uses_step_log(args)
+        if self.step_log:                                   # every step appends one row to a device-resident ring
+            trainer.enable_step_log(health=args.tb_health)
 
+    def drain(self):
+        """Drain the ring (collective; synchronises) and write its records in iteration order, with the drain's wall time."""
+        args, records = self.args, self.trainer.drain_step_log()
+        now = time.time()
+        for rec in records if self.rank0 else ():
+            pairs = step_log_pairs(rec, args.tb_every_iter, args.tb_health, args.log_every)
+            if pairs:
+                self.writer.add_scalars_at(rec['iteration'], pairs, walltime=now)
+            if args.tb_health and self.first_bad is None and not record_is_finite(rec):
+                self.first_bad = rec['iteration']
+                print('tb_health: iteration %d is the first with non-finite values (%d non-finite gradient elements, loss %r); the run '
+                      'continues' % (rec['iteration'], rec['nonfinite'], rec['losses']['loss']))
+        return records
+
+    def after_step(self, iter_num, log_images):
+        """Behind the step of iteration iter_num.  With the ring, it is read where the loop synchronises anyway (the logging
+        iterations), in front of image records (they follow the scalars of their own iteration) and when it is full -- all
+        functions of iter_num alone, so every rank drains at the same iterations."""
+        args, trainer = self.args, self.trainer
+        log_now = iter_num % args.log_every == 0
+        if self.step_log:
+            if log_now or (args.tb_images > 0 and iter_num % args.tb_images == 0) or trainer.step_log_full():
+                records = self.drain()
+                if self.rank0 and log_now:                  # printed and written from the same drained row
+                    print(console_line(iter_num, records[-1]['lr'], records[-1]['losses']))
+        elif log_now:
+            l = trainer.losses()                            # collective when world > 1: the mean over the ranks (SURVEY.md 8e)
+            if self.rank0:
+                lr_now = trainer.lr()
+                print(console_line(iter_num, lr_now, l))
+                # the reference's scalars (train.py:298-304 / 467-473), at the iterations whose losses are read back
+                self.writer.add_scalars_at(iter_num, scalar_pairs(lr_now, l))
+        if log_images:                                      # behind the scalars of the iteration, in the reference's tag order
+            self.writer.add_images_at(iter_num, trainer.take_tb_images())
+        if iter_num + 1 == 5:                               # end-to-end throughput (files -> DataLoader -> H2D -> step), start-up excluded
+            torch.cuda.synchronize()
+            self.t_mark, self.it_mark = time.time(), iter_num + 1
+
+    def throughput(self, iter_num):
+        if self.t_mark is not None and iter_num > self.it_mark:
+            torch.cuda.synchronize()
+            if self.rank0:
+                print('train throughput: %.1f images/s end to end (%d iterations of %d images, %d DataLoader workers per domain)'
+                      % ((iter_num - self.it_mark) * self.imgs_per_iter / (time.time() - self.t_mark), iter_num - self.it_mark,
+                         self.imgs_per_iter, self.args.num_workers))
+
+    def close(self):
+        if self.writer is None:
+            return
+        self.writer.close()
+        if self.args.tb_images and self.writer.seconds['calls']:
+            sec, n = self.writer.seconds, self.writer.seconds['calls']
+            print('tb_images: %d image records at %d iterations; writer thread per logging iteration: wait for the copy %.2f ms, PNG %.2f ms, '
+                  'crc32c + framing %.2f ms, file write %.2f ms' % (sec['records'], n, 1e3 * sec['wait'] / n, 1e3 * sec['png'] / n,
+                                                                    1e3 * sec['crc'] / n, 1e3 * sec['write'] / n))
+
+
+def build_trainer(args, rank, raw, resident, batch_sizes, max_len):
+    """The three drop-in modules and the trainer over them.  Draws from torch's global generator: the modules' initialisation and
+    next(iter(raw[0])), behind the loaders' construction and in front of the training."""
     encoder = Encoder(c=args.in_channels, norm=args.norm, activation=args.activation).cuda()
     seg_decoder = Decoder(num_classes=args.num_classes, norm=args.norm, activation=args.activation).cuda()
     rec_decoder = Rec_Decoder(num_classes=args.in_channels, norm='dsbn', activation=args.activation,
-                              num_domains=len(domain_idx_list)).cuda()
+                              num_domains=len(batch_sizes)).cuda()
     print('\nEncoder Params: %.3fM' % count_params(encoder))
     print('\nSeg Decoder Params: %.3fM' % count_params(seg_decoder))
     print('\nRec Decoder Params: %.3fM' % count_params(rec_decoder))
@@ -494,176 +554,165 @@ def main(args):
     Trainer = FusedTrainer if args.norm == 'bn' else ModuleTrainer
     if args.norm != 'bn' and rank == 0:
         print('norm=%s: module-level training loop (torch autograd between the HIP modules)' % args.norm)
-    trainer = Trainer(encoder, seg_decoder, rec_decoder, bsl[:len(domain_idx_list)], H, W, dataset=args.dataset,
-                           consistency=cons, lambda_rec=args.lambda_rec, lr=args.lr, total_iters=total_iters,
-                           dtype=torch.bfloat16 if (args.dtype or ('bf16' if args.norm == 'bn' else 'f32')) == 'bf16' else torch.float32)
+    trainer = Trainer(encoder, seg_decoder, rec_decoder, batch_sizes, H, W, dataset=args.dataset,
+                      consistency=cons, lambda_rec=args.lambda_rec, lr=args.lr, total_iters=total_iters,
+                      dtype=torch.bfloat16 if (args.dtype or ('bf16' if args.norm == 'bn' else 'f32')) == 'bf16' else torch.float32)
+    return (encoder, seg_decoder, rec_decoder), trainer, (H, W), total_iters
 
-    state_io = None
-    if ckpt_on:
-        # the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py); --resume: the arenas, the BatchNorm
-        # buffers and the schedule counter from the file (the host side follows immediately before the epoch loop)
-        from ramdsir import ckpt
-        state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, bsl[:len(domain_idx_list)], domain_idx_list, H, W, total_iters))
-        if resume_state is not None:
-            state_io.restore(resume_state)
-        if not args.gpu_data and args.num_workers > 0:
-            print('ckpt: model, optimizer and schedule state are restored exactly; with DataLoader worker processes the draws come from '
-                  'freshly seeded workers (use --gpu_data or --num_workers 0 for a bit-identical continuation)')
 
-    if rank == 0 and args.fused_val:
-        # the validation forward pass as one launch list over the trainer's own parameter arena (ramdsir/infer.py); only where the
-        # resident validation is in use (a test set that did not fit validates on the host, through the modules)
-        if validate is test_fundus_gpu or validate_prostate is test_prostate_gpu:
-            import functools
-            from ramdsir.infer import EvalForward
-            fused_forward = EvalForward.from_trainer(trainer)
-            validate = functools.partial(test_fundus_gpu, forward=fused_forward) if validate is test_fundus_gpu else validate
-            validate_prostate = functools.partial(test_prostate_gpu, forward=fused_forward) if validate_prostate is test_prostate_gpu \
-                else validate_prostate
-            print('fused_val: validation forward as one launch list per batch, %s storage, %s' % (
-                'bf16' if fused_forward.dtype == torch.bfloat16 else 'fp32',
-                'its own weight pack (one repack per pass)' if fused_forward.owns_pack else "the step's weight pack (no repack)"))
-        else:
-            print('fused_val: the resident validation is not in use: validating through the modules')
+def restore_host_side(args, meta, loaders, raw):
+    """The host side of a --resume snapshot, behind every start-up draw (the validation start, the loaders' construction,
+    next(iter(raw[0]))): the three generators and the cycles (replaced in `loaders`) as the snapshotted process left them at the end
+    of its epoch, and <domain>_val_log.csv cut back to its length at the snapshot.  Returns (first epoch, iter_num, previous_best)."""
+    from ramdsir import ckpt
+    ckpt.set_host_rng_state(meta['rng'])
+    for idx, st in enumerate(meta['cycles']):
+        if (st is None) != (loaders[idx] is raw[idx]):
+            raise ValueError('--resume: the snapshot cycles other loaders than this run (domain %d)' % idx)
+        if st is not None:
+            loaders[idx] = ckpt.ReplayCycle.from_state(st)
+    if os.path.exists(val_log_path(args)) and os.path.getsize(val_log_path(args)) > meta['val_log_bytes']:
+        print('resume: %s truncated from %d to %d bytes (lines of epochs that ran after the snapshot and run again)'
+              % (val_log_path(args), os.path.getsize(val_log_path(args)), meta['val_log_bytes']))
+        with open(val_log_path(args), 'r+b') as f:
+            f.truncate(meta['val_log_bytes'])
+    print('resume: %s, continuing at epoch %d (iteration %d, best %.2f)' % (args.resume, meta['epoch'] + 1, meta['iter_num'], meta['previous_best']))
+    return meta['epoch'] + 1, meta['iter_num'], meta['previous_best']
 
-    # --tb_images: one writer thread owns the event file (scalars go through its queue too, so the records keep the order of the
-    # calls); without the flag the direct writer, record for record what it always wrote
-    Writer = QueuedWriter if args.tb_images else SummaryWriter
-    writer = Writer(os.path.join(args.save_path, 'log')) if rank == 0 else None      # train.py:538
-    first_bad = []
-    if step_log:
-        # --tb_every_iter / --tb_health: every step appends one row to a device-resident ring (FusedTrainer.enable_step_log)
-        trainer.enable_step_log(health=args.tb_health)
 
-    def write_step_log():
-        """Drain the ring (collective; synchronises) and write its records in iteration order, with the drain's wall time."""
-        records = trainer.drain_step_log()
-        now = time.time()
-        for rec in records if rank == 0 else ():
-            pairs = step_log_pairs(rec, args.tb_every_iter, args.tb_health, args.log_every)
-            if pairs:
-                writer.add_scalars_at(rec['iteration'], pairs, walltime=now)
-            if args.tb_health and not first_bad and not record_is_finite(rec):
-                first_bad.append(rec['iteration'])
-                print('tb_health: iteration %d is the first with non-finite values (%d non-finite gradient elements, loss %r); the run '
-                      'continues' % (rec['iteration'], rec['nonfinite'], rec['losses']['loss']))
-        return records
+def keep_best(save_path, avg_dice, previous_best, modules):
+    """train.py:342-350: a validation at least as good as the best so far replaces model_<best>.pth.  Returns the best so far."""
+    if avg_dice is None or not avg_dice >= previous_best:
+        return previous_best
+    if previous_best != 0:
+        old = os.path.join(save_path, 'model_%.2f.pth' % previous_best)
+        if os.path.exists(old):
+            os.remove(old)
+    save_checkpoint(os.path.join(save_path, 'model_%.2f.pth' % avg_dice), *modules)
+    return avg_dice
 
-    previous_best, iter_num = 0.0, 0
-    t_mark, it_mark, imgs_per_iter = None, 0, world * sum(bsl[:len(domain_idx_list)])
-    start_epoch, epochs_here, stopped = 0, 0, False
+
+def init_process(world, local):
+    """This rank's device and, under torchrun, the process groups.  Returns the host-side rendezvous (gloo) for the points where
+    ranks wait for rank 0 on the CPU (validation): an RCCL barrier is a GPU kernel that spins until every peer has arrived."""
+    torch.cuda.set_device(local)
+    if world > 1 and not dist.is_initialized():
+        dist.init_process_group('nccl', device_id=torch.device('cuda', local))
+    return dist.new_group(backend='gloo') if world > 1 else None
+
+
+def open_state(args, trainer, fingerprint_args, resume_state):
+    """--ckpt_every / --resume, device side: the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py);
+    --resume: the arenas, the BatchNorm buffers and the schedule counter from the file (restore_host_side follows before the loop)."""
+    from ramdsir import ckpt
+    state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, *fingerprint_args))
     if resume_state is not None:
-        # the host side of the snapshot, behind every start-up draw (the loaders' construction, next(iter(raw[0])), the --gpu_val draw):
-        # the three generators and the cycles as the snapshotted process left them at the end of its epoch
-        meta = resume_state['meta']
-        ckpt.set_host_rng_state(meta['rng'])
-        for idx, st in enumerate(meta['cycles']):
-            if (st is None) != (loaders[idx] is raw[idx]):
-                raise ValueError('--resume: the snapshot cycles other loaders than this run (domain %d)' % idx)
-            if st is not None:
-                loaders[idx] = ckpt.ReplayCycle.from_state(st)
-        start_epoch, iter_num, previous_best = meta['epoch'] + 1, meta['iter_num'], meta['previous_best']
-        if os.path.exists(val_log_path(args)) and os.path.getsize(val_log_path(args)) > meta['val_log_bytes']:
-            print('resume: %s truncated from %d to %d bytes (lines of epochs that ran after the snapshot and run again)'
-                  % (val_log_path(args), os.path.getsize(val_log_path(args)), meta['val_log_bytes']))
-            with open(val_log_path(args), 'r+b') as f:
-                f.truncate(meta['val_log_bytes'])
-        print('resume: %s, continuing at epoch %d (iteration %d, best %.2f)' % (args.resume, start_epoch, iter_num, previous_best))
-        resume_state = meta = None
+        state_io.restore(resume_state)
+    if not args.gpu_data and args.num_workers > 0:
+        print('ckpt: model, optimizer and schedule state are restored exactly; with DataLoader worker processes the draws come from '
+              'freshly seeded workers (use --gpu_data or --num_workers 0 for a bit-identical continuation)')
+    return state_io
+
+
+def train_epoch(args, trainer, loaders, resident, log, iter_num):
+    """One pass over the zipped loaders; returns iter_num behind it.  One batch of look-ahead: the step of batch i also mixes batch
+    i+1 (RAM) in its tail, beside Adam and the weight repack (FusedTrainer.step next_batch; the last iteration of an epoch -- or of
+    --max_iters -- has no successor and runs the classical step)."""
+    def on_device(batches):
+        if resident is not None:                        # --gpu_data: one rd_fundus_batch / rd_prostate_batch launch
+            return resident.on_device(batches)
+        return tuple(torch.cat([b[k] for b in batches], 0).cuda(non_blocking=True) for k in range(4))       # src, trg, lam, mask
+
+    stream_it = iter(zip(*loaders))
+    cur = next(stream_it, None)
+    cur = on_device(cur) if cur is not None else None
+    while cur is not None:
+        nxt = next(stream_it, None)
+        last = nxt is None or bool(args.max_iters and iter_num + 1 >= args.max_iters)
+        nxt = None if last else on_device(nxt)
+        log_images = log.rank0 and args.tb_images > 0 and iter_num % args.tb_images == 0      # train.py:306, 475
+        if log_images:
+            trainer.arm_tb_images()                     # this step also composes the grids of its batch and starts their copy
+        trainer.step(*cur, next_batch=nxt)
+        cur = nxt
+        log.after_step(iter_num, log_images)
+        iter_num += 1
+        if args.max_iters and iter_num >= args.max_iters:
+            break
+    return iter_num
+
+
+def main(args):
+    world, rank, local = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
+    check_args(args, world)
+    if uses_ckpt(args):
+        from ramdsir import ckpt
+    resume_state = ckpt.load_file(args.resume) if args.resume else None      # an unknown version or a corrupt range is refused here
+    data_root = os.path.join(args.data_root, args.dataset)
+    # INVARIANTS of the start-up order.  Every child process (validation pool, test-loader workers) is forked before this process's
+    # first HIP call.  The draws from torch's global generator come in one order in every mode: the validation start (the test
+    # loader's base seed, or --gpu_val's one substitute draw), the loaders' construction, next(iter(raw[0])), then the training.
+    val = Validation(args, data_root) if rank == 0 else None        # rank 0 validates
+    # DataLoader workers per domain loader: the reference's 8 (train.py:558) on one GPU; under torchrun every rank has its own
+    # three loaders, so the host's cores are divided among ranks x domains (8 ranks x 3 x 8 = 192 decoder processes otherwise)
+    domain_idx_list = [int(i) for i in args.domain_idxs.split(',')]
+    preload_workers = max(1, worker_cap(args.num_workers, world, 1))     # threads decoding the resident data (<= 16)
+    args.num_workers = worker_cap(args.num_workers, world, len(domain_idx_list))
+    host_group = init_process(world, local)
+    os.makedirs(args.save_path, exist_ok=True)
+    bsl = (fundus_batch_list if args.dataset == 'fundus' else prostate_batch_list)[args.test_domain_idx][:len(domain_idx_list)]
+    raw, samplers, loaders, max_len = make_loaders(args, data_root, world, rank, bsl, domain_idx_list, replay=uses_ckpt(args))
+    resident = None
+    if args.gpu_data:
+        # decode once, keep the pixels on this GPU (ramdsir/gpu_data.py); the loaders above only draw
+        from ramdsir import gpu_data
+        t0 = time.time()
+        resident = gpu_data.preload(args.dataset, [dl.dataset for dl in raw], workers=preload_workers)
+        if rank == 0:
+            print('gpu_data: %.2f GB resident, preloaded in %.1f s with %d threads' % (resident.nbytes / 1e9, time.time() - t0,
+                                                                                       preload_workers))
+    if val is not None:
+        val.preload(preload_workers)
+    modules, trainer, (H, W), total_iters = build_trainer(args, rank, raw, resident, bsl, max_len)
+    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state) if uses_ckpt(args) else None
+    if val is not None:
+        val.bind(trainer)
+    log = TrainLog(args, trainer, rank, world * sum(bsl))
+    previous_best, iter_num, start_epoch = 0.0, 0, 0
+    if resume_state is not None:
+        start_epoch, iter_num, previous_best = restore_host_side(args, resume_state['meta'], loaders, raw)
+        resume_state = None
+    epochs_here, stopped = 0, False
     for epoch in range(start_epoch, args.epochs):
         it_epoch = iter_num
         if rank == 0:
             print('\n==> Epoch %i, learning rate = %.6f' % (epoch, args.lr if iter_num == 0 else trainer.lr()))
-        for m in (encoder, seg_decoder, rec_decoder):
+        for m in modules:
             m.train()
         t_epoch = time.time()
         for sp in samplers:
             if sp is not None:
                 sp.set_epoch(epoch)
-        def on_device(batches):
-            if resident is not None:                    # --gpu_data: one rd_fundus_batch / rd_prostate_batch launch
-                return resident.on_device(batches)
-            return tuple(torch.cat([b[k] for b in batches], 0).cuda(non_blocking=True) for k in range(4))       # src, trg, lam, mask
-
-        # one batch of look-ahead: the step of batch i also mixes batch i+1 (RAM) in its tail, beside Adam and the weight repack
-        # (FusedTrainer.step next_batch; the last iteration of an epoch -- or of --max_iters -- has no successor and runs the
-        # classical step)
-        stream_it = iter(zip(*loaders))
-        cur = next(stream_it, None)
-        cur = on_device(cur) if cur is not None else None
-        i = -1
-        while cur is not None:
-            i += 1
-            nxt = next(stream_it, None)
-            last = nxt is None or bool(args.max_iters and iter_num + 1 >= args.max_iters)
-            nxt = None if last else on_device(nxt)
-            log_images = rank == 0 and args.tb_images > 0 and iter_num % args.tb_images == 0      # train.py:306, 475
-            if log_images:
-                trainer.arm_tb_images()                 # this step also composes the grids of its batch and starts their copy
-            trainer.step(*cur, next_batch=nxt)
-            cur = nxt
-            log_now = iter_num % args.log_every == 0
-            if step_log:
-                # the step has appended its row to the device ring; read the ring where the loop synchronises anyway (the logging
-                # iterations), in front of image records (they follow the scalars of their own iteration) and when it is full --
-                # all functions of iter_num alone, so every rank drains at the same iterations (the drain is collective)
-                if log_now or (args.tb_images > 0 and iter_num % args.tb_images == 0) or trainer.step_log_full():
-                    records = write_step_log()
-                    if rank == 0 and log_now:           # printed and written from the same drained row
-                        print(console_line(iter_num, records[-1]['lr'], records[-1]['losses']))
-            elif log_now:
-                l = trainer.losses()                    # collective when world > 1: the mean over the ranks (SURVEY.md 8e)
-                if rank == 0:
-                    lr_now = trainer.lr()
-                    print(console_line(iter_num, lr_now, l))
-                    # the reference's scalars (train.py:298-304 / 467-473), at the iterations whose losses are read back
-                    writer.add_scalars_at(iter_num, scalar_pairs(lr_now, l))
-            if log_images:                              # behind the scalars of the iteration, in the reference's tag order
-                writer.add_images_at(iter_num, trainer.take_tb_images())
-            iter_num += 1
-            if iter_num == 5:                           # end-to-end throughput (files -> DataLoader -> H2D -> step), start-up excluded
-                torch.cuda.synchronize()
-                t_mark, it_mark = time.time(), iter_num
-            if args.max_iters and iter_num >= args.max_iters:
-                break
-        if t_mark is not None and iter_num > it_mark:
-            torch.cuda.synchronize()
-            if rank == 0:
-                print('train throughput: %.1f images/s end to end (%d iterations of %d images, %d DataLoader workers per domain)'
-                      % ((iter_num - it_mark) * imgs_per_iter / (time.time() - t_mark), iter_num - it_mark, imgs_per_iter, args.num_workers))
+        iter_num = train_epoch(args, trainer, loaders, resident, log, iter_num)
+        log.throughput(iter_num)
         torch.cuda.synchronize()
         t_train = time.time() - t_epoch
-        # validation on the held-out domain + keep-best checkpoint rotation (train.py:331-350); skipped when the
-        # evaluation data is not on disk (synthetic / smoke runs)
-        avg_dice = None
-        if rank == 0 and args.dataset == 'fundus' and os.path.exists(os.path.join(data_root, 'Domain%d_test.list' % (args.test_domain_idx + 1))):
-            print('Test on target domain {}'.format(args.test_domain_idx))
-            avg_dice = validate(encoder, seg_decoder, epoch, data_root, args.test_domain_idx, args.save_path, args.test_batch_size)
-        elif rank == 0 and args.dataset == 'prostate':
-            from utils.prostate_eval import DOMAIN_LIST
-            if os.path.isdir(os.path.join(data_root, DOMAIN_LIST[args.test_domain_idx])):
-                print('Test on target domain {}'.format(args.test_domain_idx))
-                avg_dice = validate_prostate(encoder, seg_decoder, epoch, data_root, args.test_domain_idx, args.save_path, args.test_batch_size)
+        # validation on the held-out domain + keep-best checkpoint rotation (train.py:331-350)
+        avg_dice = val(modules[0], modules[1], epoch) if val is not None else None
         if world > 1:
             # every rank has finished its epoch (synchronize above) and none has entered the next step's all-reduce: the
             # other ranks wait HERE, on the host (gloo), while rank 0 validates with replica 0's BatchNorm statistics (what
             # nn.DataParallel evaluates, train.py:343) -- not inside an RCCL gradient exchange with a missing peer, which
             # spins their GPUs and, past the watchdog timeout, aborts the job
             dist.barrier(group=host_group)
-        if avg_dice is not None and avg_dice >= previous_best:
-            if previous_best != 0:
-                old = os.path.join(args.save_path, 'model_%.2f.pth' % previous_best)
-                if os.path.exists(old):
-                    os.remove(old)
-            save_checkpoint(os.path.join(args.save_path, 'model_%.2f.pth' % avg_dice), encoder, seg_decoder, rec_decoder)
-            previous_best = avg_dice
+        previous_best = keep_best(args.save_path, avg_dice, previous_best, modules)
         if state_io is not None and args.ckpt_every and (epoch + 1) % args.ckpt_every == 0:
             state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), dict(
                 epoch=epoch, iter_num=iter_num, previous_best=previous_best, rng=ckpt.host_rng_state(),
                 cycles=[None if it is dl else it.state() for it, dl in zip(loaders, raw)],
                 val_log_bytes=os.path.getsize(val_log_path(args)) if os.path.exists(val_log_path(args)) else 0))
         if rank == 0:
-            t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * imgs_per_iter
+            t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * log.imgs_per_iter
             print('epoch %d: training %.2f s (%.0f images/s), validation + checkpoint %.2f s (%.0f images/s over the whole epoch)'
                   % (epoch, t_train, n_img / max(t_train, 1e-9), t_all - t_train, n_img / max(t_all, 1e-9)))
         if args.max_iters and iter_num >= args.max_iters:
@@ -672,28 +721,21 @@ def main(args):
         if args.stop_after_epochs and epochs_here >= args.stop_after_epochs and epoch + 1 < args.epochs:
             stopped = True                              # --stop_after_epochs: as a preempted job, no final_model.pth
             break
-    if step_log:
-        write_step_log()                                # the rows behind the last logging iteration
+    if log.step_log:
+        log.drain()                                         # the rows behind the last logging iteration
     if state_io is not None:
-        state_io.close()                                # the last snapshot is durable
+        state_io.close()                                    # the last snapshot is durable
         if state_io.seconds['calls']:
             print(state_io.report())
     if stopped:
         print('\nStopped after %d epochs of this process (epoch %d of %d); resume from %s'
               % (epochs_here, epoch, args.epochs, osp.join(args.save_path, 'last_state.pth')))
     elif rank == 0:
-        save_checkpoint(os.path.join(args.save_path, 'final_model.pth'), encoder, seg_decoder, rec_decoder)
+        save_checkpoint(os.path.join(args.save_path, 'final_model.pth'), *modules)
         print('\nSave Final Model to {}'.format(args.save_path))
-    if writer is not None:
-        writer.close()
-        if args.tb_images and writer.seconds['calls']:
-            sec, n = writer.seconds, writer.seconds['calls']
-            print('tb_images: %d image records at %d iterations; writer thread per logging iteration: wait for the copy %.2f ms, PNG %.2f ms, '
-                  'crc32c + framing %.2f ms, file write %.2f ms' % (sec['records'], n, 1e3 * sec['wait'] / n, 1e3 * sec['png'] / n,
-                                                                    1e3 * sec['crc'] / n, 1e3 * sec['write'] / n))
-    _close_val()
-    _VAL_GPU.clear()
-    _VAL_VOL.clear()
+    log.close()
+    if val is not None:
+        val.close()
     if world > 1:
         dist.barrier(group=host_group)
 

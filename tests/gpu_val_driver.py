@@ -24,19 +24,21 @@ def main(data_dir, ck_path, out_dir, bs):
     from utils.metrics import post_and_dice, postprocess_binary
     os.makedirs(os.path.join(out_dir, 'host'), exist_ok=True)
     os.makedirs(os.path.join(out_dir, 'gpu'), exist_ok=True)
-    loader, _ = train._val_resources(data_dir, 0, bs)
+    host = train.start_host_val(data_dir, 0, bs)
+    loader = host[0]
     ck = torch.load(ck_path, map_location='cpu')
     enc, dec = Encoder().cuda(), Decoder(num_classes=2).cuda()
     enc.load_state_dict(ck['encoder_state_dict'])
     dec.load_state_dict(ck['seg_decoder_state_dict'])
     before = {k: v.clone() for m in (enc, dec) for k, v in m.state_dict().items()}
     rng_before = (torch.get_rng_state().clone(), torch.cuda.get_rng_state().clone())
-    ret_gpu = train.test_fundus_gpu(enc, dec, 3, data_dir, 0, os.path.join(out_dir, 'gpu'), bs)
+    res = gpu_val.preload(train.fundus_testset(data_dir, 0), batch_size=bs)
+    assert res is not None, '--gpu_val: the test set does not fit in device memory'
+    ret_gpu = train.test_fundus_gpu(enc, dec, 3, res, 0, os.path.join(out_dir, 'gpu'), bs)
     untouched = all(torch.equal(v, before[k]) for m in (enc, dec) for k, v in m.state_dict().items())
     untouched = untouched and torch.equal(torch.get_rng_state(), rng_before[0]) and torch.equal(torch.cuda.get_rng_state(), rng_before[1])
-    ret_host = train.test_fundus(enc, dec, 3, data_dir, 0, os.path.join(out_dir, 'host'), bs)
+    ret_host = train.test_fundus(enc, dec, 3, data_dir, 0, os.path.join(out_dir, 'host'), bs, host=host)
     # per image: the GPU path's masks and Dice, and the host path's computed step by step as test_fundus does
-    res = train._VAL_GPU[(data_dir, 0)]
     keep = []
     dice_gpu = gpu_val.validate(enc, dec, res, bs, keep=keep)
     gpu_masks, gpu_posts = [], []
@@ -61,7 +63,7 @@ def main(data_dir, ck_path, out_dir, bs):
                 same_post.append(bool(np.array_equal(postprocess_binary(gpu_masks[i]), gpu_posts[i])))
                 sizes.append(list(masks[k].shape[1:]))
                 i += 1
-    train._close_val()
+    train.close_host_val(host)
     csv = [open(os.path.join(out_dir, d, '0_val_log.csv')).read() for d in ('host', 'gpu')]
     print('RESULT ' + json.dumps(dict(ret_host=ret_host, ret_gpu=ret_gpu, dice_host=dice_host, dice_gpu=[list(d) for d in dice_gpu],
                                       same_mask=same_mask, same_post=same_post, sizes=sizes, untouched=untouched, csv=csv,

@@ -28,13 +28,14 @@ def main(data_dir, dom, ck_path, out_dir, bs):
     dec.load_state_dict(ck['seg_decoder_state_dict'])
     before = {k: v.clone() for m in (enc, dec) for k, v in m.state_dict().items()}
     rng_before = (torch.get_rng_state().clone(), torch.cuda.get_rng_state().clone(), np.random.get_state()[1].copy())
-    ret_gpu = train.test_prostate_gpu(enc, dec, 3, data_dir, dom, os.path.join(out_dir, 'gpu'), bs)
+    res = V.preload(data_dir, PE.DOMAIN_LIST[dom], batch_size=bs)
+    assert res is not None, '--gpu_val_volumes: the volumes do not fit in device memory'
+    ret_gpu = train.test_prostate_gpu(enc, dec, 3, res, dom, os.path.join(out_dir, 'gpu'), bs)
     untouched = all(torch.equal(v, before[k]) for m in (enc, dec) for k, v in m.state_dict().items())
     untouched = untouched and torch.equal(torch.get_rng_state(), rng_before[0]) and torch.equal(torch.cuda.get_rng_state(), rng_before[1])
     untouched = untouched and np.array_equal(np.random.get_state()[1], rng_before[2])
     ret_host = train.test_prostate(enc, dec, 3, data_dir, dom, os.path.join(out_dir, 'host'), bs)
     # per volume: the GPU path's volumes and Dice, and the host path's computed step by step as evaluate_domain does
-    res = train._VAL_VOL[(data_dir, dom)]
     keep = {}
     dice_gpu = V.validate(enc, dec, res, bs, keep=keep)
     enc.eval()
