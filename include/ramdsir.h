@@ -810,6 +810,43 @@ typedef struct {
 int rd_snapshot(const rd_snap_range_t* table_host, const rd_snap_range_t* table_dev, int n, int64_t total_chunks, void* staging,
                 int64_t staging_bytes, uint64_t* sums_dev, int direction, void* stream);
 
+/* Weight averaging along the training trajectory (train.py --avg_weights, ramdsir/avg.py), csrc/avg.hip: one pass over n pairs of
+ * device ranges, src the live model (parameters, BatchNorm buffers), dst the averaged copy.  No reference counterpart: the reference
+ * keeps the last iterate only.  Range i is [src, src + bytes) and [dst, dst + bytes); bytes is a multiple of 4, src and dst are
+ * 4-byte aligned, bytes == 0 is allowed.  The src and dst ranges must not overlap each other (not checked); src is only read.
+ * The number of completed steps s is READ from *iter_dev by the kernel (rd_adam_step leaves it there: `*p.iter = it + 1`), never passed:
+ * every argument is the same at every step.  With k = s - 1 - start, per 32-bit word p of src and a of dst:
+ *     kind 1 (non-float words, e.g. the int64 num_batches_tracked):  a = p, always
+ *     kind 0 (fp32), k <= 0:                                          a = p   (the average IS the live model until averaging starts, and
+ *                                                                             the first averaged point is a copy; the bits are moved as they are)
+ *     kind 0 (fp32), k > 0:    d = p - a;  t = w * d;  a = a + t      three separately rounded fp32 operations (round to nearest even,
+ *                                                                     denormals kept), never an fma;
+ *                              w = one_minus_decay (mode 0, exponential moving average) or 1.0f / (float)(k + 1) (mode 1, the uniform
+ *                              average of the iterates start + 1, ..., s), the division correctly rounded
+ * -- numpy float32 reproduces it bit for bit (ramdsir/avg.py model()).  Work decomposition, as rd_snapshot's: range i is cut into
+ * chunks of RD_AVG_CHUNK bytes from its start (the last one ragged), chunk0 = the number of chunks of the ranges in front of it; the grid
+ * is flat over the total_chunks chunks and a workgroup finds its range by binary search over chunk0 in table_dev -- the SAME n entries
+ * in device memory, uploaded once by the caller.  table_host is read for validation only; nothing on the device is dereferenced by
+ * the host.  Within a chunk the part where src and dst are both 16-byte aligned moves with 16-byte loads and stores, the words in
+ * front of and behind it (or the whole chunk, when the two sides are aligned differently) with 4-byte accesses.
+ * Exactly ONE launch on `stream`, through the library's one launch site (none for n == 0 or when every range is empty, which
+ * succeed).  No hipMemcpyAsync / hipMemsetAsync; allocates nothing, synchronises nothing; the caller owns every buffer.  Returns,
+ * before anything is launched: -1 n < 0 (or > 2^24), a null iter_dev, or (n > 0) a null table; -2 a byte count that is negative or not
+ * a multiple of 4; -3 a misaligned src, dst or iter_dev (or a null src / dst with bytes > 0); -4 a kind other than 0 or 1; -5 a chunk0
+ * column or total_chunks that does not match the byte counts; -6 a mode other than 0 or 1; -7 mode 0 with one_minus_decay outside
+ * (0, 1) (NaN included); -8 start < 0. */
+#define RD_AVG_CHUNK 16384
+typedef struct {
+    const void* src;            /* device start of the live range */
+    void* dst;                  /* device start of the averaged range */
+    int64_t bytes;
+    int64_t chunk0;             /* first chunk of the range in the flat grid */
+    int32_t kind;               /* 0 fp32 (averaged), 1 other words (copied) */
+    int32_t pad_;
+} rd_avg_range_t;
+int rd_avg_step(const rd_avg_range_t* table_host, const rd_avg_range_t* table_dev, int n, int64_t total_chunks,
+                const int32_t* iter_dev, int mode, float one_minus_decay, int32_t start, void* stream);
+
 /* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
  * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
  * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */

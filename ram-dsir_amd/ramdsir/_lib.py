@@ -156,6 +156,16 @@ class RdSnapRange(C.Structure):
     _fields_ = [('ptr', vp), ('bytes', i64), ('offset', i64), ('chunk0', i64)]
 
 
+AVG_CHUNK = 16384                                                   # RD_AVG_CHUNK
+AVG_F32, AVG_COPY = 0, 1                                            # rd_avg_range_t.kind
+AVG_EMA, AVG_UNIFORM = 0, 1                                         # rd_avg_step's mode
+
+
+class RdAvgRange(C.Structure):
+    """rd_avg_range_t (include/ramdsir.h): one range pair of rd_avg_step's table."""
+    _fields_ = [('src', vp), ('dst', vp), ('bytes', i64), ('chunk0', i64), ('kind', i32), ('pad_', i32)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -240,6 +250,7 @@ _SIGS = {
     'rd_step_log': (C.c_int, [C.POINTER(RdStepLog), vp]),
     'rd_step_log_workspace': (i64, [i64]),
     'rd_snapshot': (C.c_int, [C.POINTER(RdSnapRange), vp, C.c_int, i64, vp, i64, vp, C.c_int, vp]),
+    'rd_avg_step': (C.c_int, [C.POINTER(RdAvgRange), vp, C.c_int, i64, vp, C.c_int, f32, i32, vp]),
     'rd_crc32c':(C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),

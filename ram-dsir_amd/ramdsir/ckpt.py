@@ -8,7 +8,8 @@ and never reads one back into a trainer.
 The file (torch.save of plain containers): format / version, the range table (name, dtype, shape, offset, bytes, the two checksums),
 the blob as one uint8 tensor, the host meta (epoch, iter_num, previous_best, the three host generators, the replay state of every
 cycled loader, the byte length of the validation CSV) and the fingerprint of the run (arguments, geometry, parameter manifest).
-`state_dicts(state)` turns it into the reference's three state_dicts without a GPU.
+`state_dicts(state)` turns it into the reference's three state_dicts without a GPU.  With train.py --avg_weights the ranges of the
+averaged model ('avg/...', ramdsir/avg.py) follow the trainer's and its settings sit under meta['avg_weights'] (compare_avg_weights).
 
 Checksums of the little-endian uint32 words w[0 .. m) of a range: s1 = sum w[i], s2 = sum (i + 1) w[i], both mod 2^64 (`checksums`
 is the numpy model the kernel equals bit for bit; s2 depends on the order of the words, s1 does not).
@@ -126,6 +127,28 @@ def compare_fingerprints(saved, current):
             if f == 'manifest':
                 a, b = next(((x, y) for x, y in zip(a or [], b or []) if x != y), (len(a or []), len(b or [])))
             raise ValueError('--resume: the snapshot was taken with %s = %r, this run has %r' % (f, a, b))
+
+
+AVG_PREFIX = 'avg/'             # the ranges of the averaged model (ramdsir/avg.py named_ranges)
+AVG_SETTINGS = ('mode', 'decay', 'start')
+
+
+def compare_avg_weights(state, current):
+    """--resume with / without --avg_weights.  current: the run's settings (avg.WeightAverage.settings()) or None when the flag is off.
+    ValueError naming avg_weights where the file has no averaged ranges and the run wants them, has them and the run does not, or was
+    taken under other settings: an average cannot be made up, dropped or continued under another rule in the middle of a run."""
+    saved = (state.get('meta') or {}).get('avg_weights')
+    has = any(e['name'].startswith(AVG_PREFIX) for e in state['table'])
+    if current is not None and not (has and saved):
+        raise ValueError('--resume: the snapshot holds no averaged model (it was taken without --avg_weights); this run has avg_weights = %r'
+                         % (dict(current),))
+    if current is None and (has or saved):
+        raise ValueError('--resume: the snapshot holds an averaged model (avg_weights = %r); this run was started without --avg_weights'
+                         % ({k: saved.get(k) for k in AVG_SETTINGS} if saved else None,))
+    if current is not None:
+        for k in AVG_SETTINGS:
+            if saved.get(k) != current.get(k):
+                raise ValueError('--resume: the snapshot was taken with avg_weights %s = %r, this run has %r' % (k, saved.get(k), current.get(k)))
 
 
 # ------------------------------------------------------------------------------------------------------------- the file
@@ -266,11 +289,13 @@ class TrainState:
     n lines of sums behind it, so ONE copy brings both to the host), its pinned twin, the device range table, a side stream and the writer
     thread.  snapshot() costs the training stream one rd_snapshot; restore() is upload() + scatter()."""
 
-    def __init__(self, trainer, fp=None):
+    def __init__(self, trainer, fp=None, extra=None):
+        """extra: [(name, tensor)] appended behind trainer_ranges(trainer) -- device ranges that belong to the run's state without
+        belonging to the trainer (the averaged model of --avg_weights: avg.WeightAverage.named_ranges())."""
         if getattr(trainer, '_graphs', False):
             raise RuntimeError('TrainState: a captured hipGraph replays a fixed launch list (use_graph=True)')
         self.trainer, self.fingerprint = trainer, fp
-        self.named = trainer_ranges(trainer)
+        self.named = trainer_ranges(trainer) + list(extra or ())
         self.table, self.blob_bytes = layout(self.named)
         self.n = n = len(self.named)
         dev = trainer.bank.device

@@ -28,7 +28,7 @@ class FusedTrainer:
                               options=dict(side_cus=0, rec_cus=0) if use_graph else None)
         self.ts.wpack.refresh()
         self._primed, self._graphs, self._announced = False, bool(use_graph), None
-        self._tb, self._tb_pending, self._tb_hook, self._log = None, None, None, None
+        self._tb, self._tb_pending, self._tb_hook, self._log, self._avg = None, None, None, None, None
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -88,19 +88,36 @@ class FusedTrainer:
         self._tb_hook = hook
 
     def _arm_after_step(self):
-        """TrainStep.arm_after_step holds ONE one-shot hook; the image grids (armed for single steps) and the step log (every step, once
-        enabled) share it: one closure per step runs whichever of the two apply.  Nothing is armed when neither does."""
+        """TrainStep.arm_after_step holds ONE one-shot hook; the image grids (armed for single steps), the step log and the weight
+        average (every step, once enabled) share it: one closure per step runs whichever of the three apply, in the order step log,
+        averaging, image compose -- the two per-step launches of a few microseconds first, the compose and the start of its copy to
+        the host last.  All three only read the step's buffers, so the order changes no result.  Nothing is armed when none applies."""
         tb, self._tb_hook = self._tb_hook, None
-        log = self._log
-        if tb is None and log is None:
+        log, avg = self._log, self._avg
+        if tb is None and log is None and avg is None:
             return
 
         def hook(slot):
             if log is not None:
                 log.append(torch.cuda.current_stream().cuda_stream)
+            if avg is not None:
+                avg.enqueue(torch.cuda.current_stream().cuda_stream)
             if tb is not None:
                 tb(slot)
         self.ts.arm_after_step(hook)
+
+    def enable_avg_weights(self, mode='ema', decay=0.999, start=0):
+        """From now on every step() is followed by one rd_avg_step launch (ramdsir/avg.py) that moves a second copy of the model -- the
+        parameter arena and every BatchNorm buffer, initialised HERE as a copy of the live ones -- towards the live model: an exponential
+        moving average (mode 'ema', `decay`) or the uniform average of the iterates behind iteration `start` ('uniform').  The launch
+        sits on the main stream behind the step's last launch (TrainStep.arm_after_step), reads the device-side iteration counter
+        itself and only reads the trainer's buffers: training is bit-identical with and without it.  Data parallel: rank-local, no
+        collective.  Returns the avg.WeightAverage.  Not with use_graph=True."""
+        if self._graphs:
+            raise RuntimeError('enable_avg_weights: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        from . import avg
+        self._avg = avg.WeightAverage(self, mode, decay, start)
+        return self._avg
 
     def enable_step_log(self, health=False, rows=256):
         """From now on every step() appends one row to a device-resident ring (ramdsir/step_log.py, rd_step_log): the losses, the lr and

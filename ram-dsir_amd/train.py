@@ -17,7 +17,10 @@ grids (train.py:306-329, 475-496) are opt-in (--tb_images: composed on the GPU, 
 (train.py:534-536) is not reproduced; (v) --ckpt_every N snapshots the whole training state (model, Adam moments, BatchNorm buffers,
 schedule counter, host generators, the cycled loaders' replay lists) every N epochs through one HIP gather and a writer thread, --resume
 continues from such a file -- bit-identically with --gpu_data or --num_workers 0 -- and --stop_after_epochs slices a run into jobs
-(ramdsir/ckpt.py); the reference can only start from a fresh initialisation.
+(ramdsir/ckpt.py); the reference can only start from a fresh initialisation; (vi) --avg_weights ema | uniform keeps a second copy of
+the model, averaged along the trajectory by one HIP launch behind every step (ramdsir/avg.py, rd_avg_step), validates it beside the live
+one where --fused_val is in use (<target>_val_log_avg.csv, model_avg_%.2f.pth) and writes final_model_avg.pth; the reference keeps the
+last iterate only.
 """
 import argparse
 import os
@@ -46,6 +49,7 @@ from utils.tfevents import SummaryWriter, QueuedWriter
 
 fundus_batch_list = [[3, 6, 7], [2, 7, 7], [2, 4, 10], [2, 4, 10]]              # train.py:35-38
 prostate_batch_list = [[2, 2, 2, 2, 2]] * 6                                       # train.py:40-45
+AVG_DECAY = 0.999                                                                 # --avg_decay where it is not given
 
 
 class Compose(object):
@@ -125,6 +129,16 @@ def parse_args(argv=None):
     p.add_argument('--stop_after_epochs', type=int, default=0, metavar='K',
                    help='leave after K epochs of THIS process, once the last snapshot is on disk, without writing final_model.pth -- as a '
                         'preempted job would; needs --ckpt_every (slices a run into jobs)')
+    p.add_argument('--avg_weights', type=str, default=None, choices=['ema', 'uniform'],
+                   help='keep a second copy of the model averaged along the training trajectory -- an exponential moving average, or the '
+                        'uniform average of every iterate from --avg_start on -- by one HIP launch behind every step (ramdsir/avg.py, '
+                        'rd_avg_step); with --fused_val it is validated per epoch beside the live model (<target>_val_log_avg.csv, '
+                        'model_avg_%%.2f.pth); final_model_avg.pth at the end; BatchNorm running statistics are averaged like parameters; '
+                        '--norm bn only; off by default')
+    p.add_argument('--avg_decay', type=float, default=None, metavar='D', help='--avg_weights ema: the decay, in (0, 1); default %g' % AVG_DECAY)
+    p.add_argument('--avg_start', type=int, default=None, metavar='ITER',
+                   help='--avg_weights: the iteration from which on iterates are averaged; until then the averaged model is a copy of the '
+                        'live one; default 0')
     return p.parse_args(argv)
 
 
@@ -169,23 +183,25 @@ def close_host_val(host):
     host[1].join()
 
 
-def report_fundus(dices, epoch, datasetTest, output_path, batch_size):
-    """The end of train.py:91-132: the mean cup / disc Dice of [(cup, disc)] per image, the console line, the reference's CSV line."""
+def report_fundus(dices, epoch, datasetTest, output_path, batch_size, suffix=''):
+    """The end of train.py:91-132: the mean cup / disc Dice of [(cup, disc)] per image, the console line, the reference's CSV line
+    (in <target>_val_log<suffix>.csv: '_avg' for the averaged model of --avg_weights)."""
     cup = disc = 0.0
     for c, d in dices:
         cup, disc = cup + c, disc + d
     cup, disc = cup / max(len(dices), 1), disc / max(len(dices), 1)
     print('val_cup_dice : {}, val_disc_dice : {}'.format(cup, disc))
-    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
+    with open(osp.join(output_path, str(datasetTest) + '_val_log%s.csv' % suffix), 'a') as f:
         f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['cup dice coefficence: '] + [cup] +
                                    ['disc dice coefficence: '] + [disc]])) + '\n')
     return (cup + disc) * 100.0 / 2
 
 
-def report_prostate(val_dice, epoch, datasetTest, output_path, batch_size):
-    """The end of train.py:134-192: the console line and the reference's CSV line of the mean volume Dice."""
+def report_prostate(val_dice, epoch, datasetTest, output_path, batch_size, suffix=''):
+    """The end of train.py:134-192: the console line and the reference's CSV line of the mean volume Dice (in
+    <target>_val_log<suffix>.csv)."""
     print('val_dice : {}'.format(val_dice))
-    with open(osp.join(output_path, str(datasetTest) + '_val_log.csv'), 'a') as f:
+    with open(osp.join(output_path, str(datasetTest) + '_val_log%s.csv' % suffix), 'a') as f:
         f.write(','.join(map(str, [['batch-size: '] + [batch_size] + [epoch] + ['dice coefficence: '] + [val_dice]])) + '\n')
     return val_dice * 100.0
 
@@ -211,13 +227,14 @@ def test_fundus(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path,
     return report_fundus(dices, epoch, datasetTest, output_path, batch_size)
 
 
-def test_fundus_gpu(encoder, seg_decoder, epoch, resident, datasetTest, output_path, batch_size=8, forward=None):
+def test_fundus_gpu(encoder, seg_decoder, epoch, resident, datasetTest, output_path, batch_size=8, forward=None, suffix=''):
     """test_fundus with everything after the forward pass on the GPU (--gpu_val; ramdsir/gpu_val.py, csrc/val_post.hip): the same
     batches in list order through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.
-    resident: gpu_val.preload's set.  forward (--fused_val): the infer.EvalForward that runs the forward pass instead of the modules."""
+    resident: gpu_val.preload's set.  forward (--fused_val): the infer.EvalForward that runs the forward pass instead of the modules
+    (its parameters are the model that is validated); suffix: of the CSV's name."""
     from ramdsir import gpu_val
     return report_fundus(gpu_val.validate(encoder, seg_decoder, resident, batch_size, forward=forward), epoch, datasetTest, output_path,
-                         batch_size)
+                         batch_size, suffix)
 
 
 def test_prostate(encoder, seg_decoder, epoch, data_dir, datasetTest, output_path, batch_size=8, dataset='prostate'):
@@ -231,15 +248,16 @@ def test_prostate(encoder, seg_decoder, epoch, data_dir, datasetTest, output_pat
     return report_prostate(val_dice, epoch, datasetTest, output_path, batch_size)
 
 
-def test_prostate_gpu(encoder, seg_decoder, epoch, resident, datasetTest, output_path, batch_size=8, forward=None):
+def test_prostate_gpu(encoder, seg_decoder, epoch, resident, datasetTest, output_path, batch_size=8, forward=None, suffix=''):
     """test_prostate on the resident volumes (--gpu_val_volumes; ramdsir/gpu_val_volumes.py, csrc/val_volume.hip): the same batches
     through the same modules, the same CSV line, the same return value; Dice from integer counts, read back once.  resident:
-    gpu_val_volumes.preload's volumes.  forward (--fused_val): the infer.EvalForward that runs the forward pass instead of the modules."""
+    gpu_val_volumes.preload's volumes.  forward (--fused_val): the infer.EvalForward that runs the forward pass instead of the modules;
+    suffix: of the CSV's name."""
     from ramdsir import gpu_val_volumes
     val_dice = 0.0
     for d in gpu_val_volumes.validate(encoder, seg_decoder, resident, batch_size, forward=forward):
         val_dice += d
-    return report_prostate(val_dice / max(len(resident), 1), epoch, datasetTest, output_path, batch_size)
+    return report_prostate(val_dice / max(len(resident), 1), epoch, datasetTest, output_path, batch_size, suffix)
 
 
 def val_mode(args, on_disk, fits=True):
@@ -335,6 +353,18 @@ class Validation:
             return test_prostate(*models, self.data_root, *tail)
         return (test_fundus_gpu if self.fundus else test_prostate_gpu)(*models, self.resident, *tail, forward=self.forward)
 
+    def averaged(self, avg, encoder, seg_decoder, epoch):
+        """--avg_weights: a second pass of the resident validation, through the fused forward over the AVERAGED bank
+        (avg.WeightAverage.eval_forward(); the pass begins with its refresh(): the averaged weights repacked, the frozen BatchNorm
+        coefficients from the averaged running statistics), into <target>_val_log_avg.csv.  The average Dice in percent; None where
+        the fused forward is not in use -- the modules' forward reads the live parameters."""
+        if self.mode != 'fused':
+            return None
+        print('Test the averaged model on target domain {}'.format(self.domain))
+        test = test_fundus_gpu if self.fundus else test_prostate_gpu
+        return test(encoder, seg_decoder, epoch, self.resident, self.domain, self.args.save_path, self.batch_size,
+                    forward=avg.eval_forward(), suffix='_avg')
+
     def close(self):
         if self.host is not None:
             close_host_val(self.host)
@@ -399,8 +429,18 @@ def uses_ckpt(args):
     return bool(args.ckpt_every or args.resume or args.stop_after_epochs)
 
 
-def val_log_path(args):
-    return osp.join(args.save_path, str(args.test_domain_idx) + '_val_log.csv')
+def uses_avg(args):
+    """--avg_weights turns the averaged model on (ramdsir/avg.py); without it the run allocates and launches nothing for it."""
+    return args.avg_weights is not None
+
+
+def avg_settings(args):
+    """(mode, decay, start) of --avg_weights with the defaults of the two flags that were not given."""
+    return args.avg_weights, AVG_DECAY if args.avg_decay is None else args.avg_decay, 0 if args.avg_start is None else args.avg_start
+
+
+def val_log_path(args, suffix=''):
+    return osp.join(args.save_path, str(args.test_domain_idx) + '_val_log%s.csv' % suffix)
 
 
 def console_line(iter_num, lr_now, l):
@@ -457,6 +497,18 @@ def check_args(args, world):
     if uses_ckpt(args) and world > 1:
         raise ValueError('--ckpt_every / --resume / --stop_after_epochs run in one process: BatchNorm buffers, generators and replay lists '
                          'are rank-local (WORLD_SIZE=%d)' % world)
+    if not uses_avg(args) and (args.avg_decay is not None or args.avg_start is not None):
+        raise ValueError('--avg_decay / --avg_start shape the averaged model: they need --avg_weights')
+    if uses_avg(args) and args.norm != 'bn':
+        raise ValueError('--avg_weights averages the fused step\'s parameter arena behind its Adam launch: --norm %s trains through the '
+                         'modules, whose Adam is torch\'s' % args.norm)
+    if args.avg_weights == 'uniform' and args.avg_decay is not None:
+        raise ValueError('--avg_decay is the decay of --avg_weights ema; uniform weighs every iterate alike')
+    # (the kernel's weight is 1 - decay formed in float32: a decay that rounds to 1 there is refused with the ones outside the interval)
+    if args.avg_decay is not None and not (0.0 < args.avg_decay < 1.0 and 0.0 < float(np.float32(1) - np.float32(args.avg_decay)) < 1.0):
+        raise ValueError('--avg_decay takes a decay in (0, 1), got %r' % args.avg_decay)
+    if args.avg_start is not None and args.avg_start < 0:
+        raise ValueError('--avg_start takes an iteration number, got %d' % args.avg_start)
 
 
 class TrainLog:
@@ -580,15 +632,32 @@ def restore_host_side(args, meta, loaders, raw):
     return meta['epoch'] + 1, meta['iter_num'], meta['previous_best']
 
 
-def keep_best(save_path, avg_dice, previous_best, modules):
-    """train.py:342-350: a validation at least as good as the best so far replaces model_<best>.pth.  Returns the best so far."""
+def restore_avg_host_side(args, meta):
+    """--resume with --avg_weights: <domain>_val_log_avg.csv cut back to its length at the snapshot, as restore_host_side cuts the main
+    one.  Returns previous_best_avg."""
+    saved, path = meta['avg_weights'], val_log_path(args, '_avg')
+    if os.path.exists(path) and os.path.getsize(path) > saved['val_log_bytes']:
+        print('resume: %s truncated from %d to %d bytes' % (path, os.path.getsize(path), saved['val_log_bytes']))
+        with open(path, 'r+b') as f:
+            f.truncate(saved['val_log_bytes'])
+    return saved['previous_best_avg']
+
+
+def keep_best(save_path, avg_dice, previous_best, modules, averaged=None):
+    """train.py:342-350: a validation at least as good as the best so far replaces model_<best>.pth.  Returns the best so far.
+    averaged (--avg_weights): the avg.WeightAverage whose model was validated -- the same rotation over model_avg_<best>.pth, with the
+    averaged state_dicts under the reference's three keys."""
+    name = 'model_%.2f.pth' if averaged is None else 'model_avg_%.2f.pth'
     if avg_dice is None or not avg_dice >= previous_best:
         return previous_best
     if previous_best != 0:
-        old = os.path.join(save_path, 'model_%.2f.pth' % previous_best)
+        old = os.path.join(save_path, name % previous_best)
         if os.path.exists(old):
             os.remove(old)
-    save_checkpoint(os.path.join(save_path, 'model_%.2f.pth' % avg_dice), *modules)
+    if averaged is None:
+        save_checkpoint(os.path.join(save_path, name % avg_dice), *modules)
+    else:
+        torch.save(dict(averaged.state_dicts()), os.path.join(save_path, name % avg_dice))
     return avg_dice
 
 
@@ -601,11 +670,14 @@ def init_process(world, local):
     return dist.new_group(backend='gloo') if world > 1 else None
 
 
-def open_state(args, trainer, fingerprint_args, resume_state):
+def open_state(args, trainer, fingerprint_args, resume_state, avg=None):
     """--ckpt_every / --resume, device side: the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py);
-    --resume: the arenas, the BatchNorm buffers and the schedule counter from the file (restore_host_side follows before the loop)."""
+    --resume: the arenas, the BatchNorm buffers and the schedule counter from the file (restore_host_side follows before the loop).
+    avg (--avg_weights): the averaged model's ranges go behind the trainer's; a file and a run that disagree about them are refused."""
     from ramdsir import ckpt
-    state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, *fingerprint_args))
+    if resume_state is not None:
+        ckpt.compare_avg_weights(resume_state, avg.settings() if avg is not None else None)
+    state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, *fingerprint_args), extra=avg.named_ranges() if avg is not None else None)
     if resume_state is not None:
         state_io.restore(resume_state)
     if not args.gpu_data and args.num_workers > 0:
@@ -674,13 +746,20 @@ def main(args):
     if val is not None:
         val.preload(preload_workers)
     modules, trainer, (H, W), total_iters = build_trainer(args, rank, raw, resident, bsl, max_len)
-    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state) if uses_ckpt(args) else None
+    # --avg_weights: the second bank, a copy of the initial model (rank-local under data parallelism, as the BatchNorm buffers are)
+    avg = trainer.enable_avg_weights(*avg_settings(args)) if uses_avg(args) else None
+    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg) if uses_ckpt(args) else None
     if val is not None:
         val.bind(trainer)
+        if avg is not None and val.mode != 'fused':
+            print('avg_weights: the averaged model is maintained and written at the end, but not validated per epoch (that pass is the '
+                  'fused forward of --gpu_val / --gpu_val_volumes with --fused_val)')
     log = TrainLog(args, trainer, rank, world * sum(bsl))
-    previous_best, iter_num, start_epoch = 0.0, 0, 0
+    previous_best, iter_num, start_epoch, previous_best_avg = 0.0, 0, 0, 0.0
     if resume_state is not None:
         start_epoch, iter_num, previous_best = restore_host_side(args, resume_state['meta'], loaders, raw)
+        if avg is not None:
+            previous_best_avg = restore_avg_host_side(args, resume_state['meta'])
         resume_state = None
     epochs_here, stopped = 0, False
     for epoch in range(start_epoch, args.epochs):
@@ -706,11 +785,23 @@ def main(args):
             # spins their GPUs and, past the watchdog timeout, aborts the job
             dist.barrier(group=host_group)
         previous_best = keep_best(args.save_path, avg_dice, previous_best, modules)
+        if avg is not None:
+            # the averaged model behind the live one: its own CSV, its own keep-best rotation; the other ranks wait on the host again
+            if val is not None:
+                previous_best_avg = keep_best(args.save_path, val.averaged(avg, modules[0], modules[1], epoch), previous_best_avg, modules,
+                                              averaged=avg)
+            if world > 1:
+                dist.barrier(group=host_group)
         if state_io is not None and args.ckpt_every and (epoch + 1) % args.ckpt_every == 0:
-            state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), dict(
+            meta = dict(
                 epoch=epoch, iter_num=iter_num, previous_best=previous_best, rng=ckpt.host_rng_state(),
                 cycles=[None if it is dl else it.state() for it, dl in zip(loaders, raw)],
-                val_log_bytes=os.path.getsize(val_log_path(args)) if os.path.exists(val_log_path(args)) else 0))
+                val_log_bytes=os.path.getsize(val_log_path(args)) if os.path.exists(val_log_path(args)) else 0)
+            if avg is not None:
+                avg_log = val_log_path(args, '_avg')
+                meta['avg_weights'] = dict(avg.settings(), previous_best_avg=previous_best_avg,
+                                           val_log_bytes=os.path.getsize(avg_log) if os.path.exists(avg_log) else 0)
+            state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), meta)
         if rank == 0:
             t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * log.imgs_per_iter
             print('epoch %d: training %.2f s (%.0f images/s), validation + checkpoint %.2f s (%.0f images/s over the whole epoch)'
@@ -732,6 +823,8 @@ def main(args):
               % (epochs_here, epoch, args.epochs, osp.join(args.save_path, 'last_state.pth')))
     elif rank == 0:
         save_checkpoint(os.path.join(args.save_path, 'final_model.pth'), *modules)
+        if avg is not None:
+            torch.save(dict(avg.state_dicts()), os.path.join(args.save_path, 'final_model_avg.pth'))
         print('\nSave Final Model to {}'.format(args.save_path))
     log.close()
     if val is not None:
