@@ -847,6 +847,71 @@ typedef struct {
 int rd_avg_step(const rd_avg_range_t* table_host, const rd_avg_range_t* table_dev, int n, int64_t total_chunks,
                 const int32_t* iter_dev, int mode, float one_minus_decay, int32_t start, void* stream);
 
+/* Guarded optimizer step (train.py --clip_grad_norm / --skip_nonfinite, ramdsir/guard.py), csrc/guard.hip + csrc/loss.hip: what
+ * stands in front of the reference's `loss.backward(); optimizer.step()` (code/train.py:285-287) when the user asks for it -- the
+ * gradient of the whole arena is clipped by its global norm (torch.nn.utils.clip_grad_norm_ over the one optimizer), and a step whose
+ * gradient is not finite leaves no trace in the model state.  No reference counterpart: the reference steps on whatever it gets.
+ * Everything is decided on the device: the three entry points communicate through ONE device-resident rd_guard_state_t, which every
+ * launch below reads or writes through its device pointer; the host reads it only where it synchronises anyway.
+ *
+ * rd_grad_guard: two launches, the decomposition of rd_step_log's health pass over ONE group.  (1) the n elements of `grad` are cut
+ * into chunks of RD_LOG_CHUNK from its start; workgroup c sums g * g in fp64 over the FINITE elements of chunk c in a fixed order and
+ * counts the others into partial[c] = {double sum, int64 count}; 16-byte loads on the aligned part of a chunk with a scalar head and
+ * tail, for any 4-byte alignment of grad.  (2) one workgroup: lane l of wave 0 adds partials l, l + 64, ... in ascending order, then
+ * the 64 lanes in the fixed xor tree (offsets 32, 16, ..., 1) -- no atomics -- and thread 0 writes
+ *     norm      = (float)sqrt(sum)                       (the fp64 square root, rounded once to fp32)
+ *     nonfinite = the count                              (n <= 2^24: it fits)
+ *     skip      = nonfinite > 0 || !isfinite(norm)       (squares that overflow fp32 but not fp64 give a norm that is +Inf as a float)
+ *     scale     = skip ? 1 : max_norm > 0 ? fminf(max_norm / (norm + 1e-6f), 1) : 1      separately rounded fp32 operations
+ *     steps += 1;  clipped += (scale < 1 && !skip);  skipped += skip
+ * ramdsir/guard.py model() is the same arithmetic in numpy, bit for bit.  The gradient is only read.  workspace:
+ * rd_grad_guard_workspace(n) bytes, 8-byte aligned, contents irrelevant before and after.  Returns, before anything is launched:
+ * -1 a null descriptor / grad / workspace / state or a misaligned one (grad 4, workspace and state 8 bytes), -2 n < 1 or n > 2^24
+ * (rd_step_log's bound), -3 a max_norm that is negative or not finite (0: clipping off).
+ *
+ * rd_adam_step_guarded: rd_adam_step with two differences.  Its prepare launch forms the bias corrections from the number of updates
+ * APPLIED, t = max(1, iter + 1 - guard->skipped) (the state['step'] of a skipped optimizer.step()); lr, hyper_out[0], hyper_out[3]
+ * and `*iter += 1` are exactly rd_adam_step's -- the reference's lr is a function of iter_num (code/train.py:289).  Its update launch
+ * returns at once when guard->skip is set (nothing is stored), and otherwise uses g = grad[i] * guard->scale (one rounded fp32
+ * multiplication; scale == 1 is the identity) in rd_adam_step's arithmetic.  Returns -1 for a null descriptor or state, or n < 1.
+ *
+ * rd_guard_sync: ONE launch over n range pairs {live, shadow, bytes, chunk0}: with guard->skip set, live <- shadow (the BatchNorm
+ * buffers the forward pass of the skipped step has moved are rolled back); otherwise shadow <- live (the last good step is
+ * remembered).  A byte copy: int64 ranges and NaN bit patterns pass through untouched.  Work decomposition and validation codes are
+ * rd_avg_step's, with RD_GUARD_CHUNK for RD_AVG_CHUNK: -1 n < 0 (or > 2^24), a null guard_dev, or (n > 0) a null table; -2 a byte
+ * count that is negative or not a multiple of 4; -3 a misaligned live / shadow / guard_dev (or a null live / shadow with bytes > 0);
+ * -5 a chunk0 column or total_chunks that does not match the byte counts.  The live and shadow ranges must not overlap (not checked).
+ * None of the three allocates, synchronises or copies anything; every launch goes through the library's one launch site. */
+#define RD_GUARD_CHUNK 16384
+typedef struct {
+    float norm;                 /* global gradient norm of the last guarded step (finite elements) */
+    float scale;                /* what that step multiplied its gradient by */
+    int32_t skip;               /* 1: that step was skipped */
+    int32_t nonfinite;          /* its number of non-finite gradient elements */
+    int64_t steps;              /* guarded steps so far */
+    int64_t clipped;            /* of these, steps with scale < 1 */
+    int64_t skipped;            /* of these, skipped steps */
+} rd_guard_state_t;
+typedef struct {
+    const float* grad;          /* device arena */
+    int64_t n;                  /* elements */
+    float max_norm;             /* 0: no clipping */
+    int32_t pad_;
+    void* workspace;            /* device */
+    rd_guard_state_t* state;    /* device */
+} rd_grad_guard_t;
+typedef struct {
+    void* live;                 /* device start of the live range */
+    void* shadow;               /* device start of its shadow copy */
+    int64_t bytes;
+    int64_t chunk0;             /* first chunk of the range in the flat grid */
+} rd_guard_range_t;
+int64_t rd_grad_guard_workspace(int64_t n);
+int rd_grad_guard(const rd_grad_guard_t* p, void* stream);
+int rd_adam_step_guarded(const rd_adam_t* p, const rd_guard_state_t* guard_dev, void* stream);
+int rd_guard_sync(const rd_guard_range_t* table_host, const rd_guard_range_t* table_dev, int n, int64_t total_chunks,
+                  const rd_guard_state_t* guard_dev, void* stream);
+
 /* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
  * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
  * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */

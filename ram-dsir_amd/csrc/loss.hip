@@ -356,12 +356,12 @@ __global__ __launch_bounds__(64 * RD_MAX_GROUPS) void rec_loss_final_kernel(cons
 }
 
 // ----------------------------------------------------------------------------------- Adam
-__global__ void adam_prepare_kernel(const rd_adam_t p) {
-    const int it = *p.iter;
+// `applied`: the number of updates applied before this one -- the iteration number itself, or (guarded step) less the skipped steps
+__device__ __forceinline__ void adam_prepare(const rd_adam_t& p, int it, long long applied) {
     // LR in force at iteration `it` was written after iteration it-1 from ITS iter_num (train.py:289)
     double lr = p.base_lr;
     if (it > 0) lr = (double)p.base_lr * pow(1.0 - (double)(it - 1) / (double)p.total_iters, 0.9);
-    const double t = (double)(it + 1);
+    const double t = (double)(applied + 1);
     p.hyper_out[0] = (float)lr;
     p.hyper_out[1] = (float)(1.0 - pow((double)p.beta1, t));
     p.hyper_out[2] = (float)(1.0 - pow((double)p.beta2, t));
@@ -369,11 +369,29 @@ __global__ void adam_prepare_kernel(const rd_adam_t p) {
     *p.iter = it + 1;
 }
 
-__global__ __launch_bounds__(256) void adam_update_kernel(const rd_adam_t p) {
+__global__ void adam_prepare_kernel(const rd_adam_t p) {
+    const int it = *p.iter;
+    adam_prepare(p, it, it);
+}
+
+// the guarded step (rd_adam_step_guarded): bias corrections from the updates APPLIED, t = max(1, iter + 1 - skipped) -- rd_grad_guard
+// has counted this step already when it skips it; the schedule words and the counter are the plain step's
+__global__ void adam_prepare_guarded_kernel(const rd_adam_t p, const rd_guard_state_t* __restrict__ guard) {
+    const int it = *p.iter;
+    const long long applied = (long long)it - guard->skipped;
+    adam_prepare(p, it, applied > 0 ? applied : 0);
+}
+
+// ONE body for both update kernels.  GUARDED = false is rd_adam_step's kernel as it always was (scale is not read);
+// GUARDED = true multiplies the gradient by the guard's scale first: one rounded fp32 product, then the same expressions.
+// The grid-stride bounds are formed in the kernels: read there, the launch geometry comes from scalar loads of the kernel's own
+// arguments, as it did in rd_adam_step's kernel before the body was shared.
+template <bool GUARDED>
+__device__ __forceinline__ void adam_update(const rd_adam_t& p, float scale, int64_t first, int64_t stride) {
     const float lr = p.hyper_out[0], bc1 = p.hyper_out[1], bc2 = p.hyper_out[2];
     const float sq_bc2 = sqrtf(bc2);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float g = p.grad[i];
+    for (int64_t i = first; i < p.n; i += stride) {
+        const float g = GUARDED ? __fmul_rn(p.grad[i], scale) : p.grad[i];
         const float m = p.beta1 * p.exp_avg[i] + (1.f - p.beta1) * g;
         const float v = p.beta2 * p.exp_avg_sq[i] + (1.f - p.beta2) * g * g;
         p.exp_avg[i] = m;
@@ -382,6 +400,16 @@ __global__ __launch_bounds__(256) void adam_update_kernel(const rd_adam_t p) {
         const float denom = sqrtf(v) / sq_bc2 + p.eps;
         p.param[i] -= step * (m / denom);
     }
+}
+
+__global__ __launch_bounds__(256) void adam_update_kernel(const rd_adam_t p) {
+    adam_update<false>(p, 1.f, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// a skipped step stores nothing: the branch is uniform over the grid
+__global__ __launch_bounds__(256) void adam_update_guarded_kernel(const rd_adam_t p, const rd_guard_state_t* __restrict__ guard) {
+    if (guard->skip != 0) return;
+    adam_update<true>(p, guard->scale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // rd_zero: every range in one launch (16-byte stores; the last bytes of a range whose size is not a multiple of 16 one by one)
@@ -476,6 +504,19 @@ int rd_adam_step(const rd_adam_t* p, void* stream) {
     int64_t nb = (p->n + 255) / 256;
     if (nb > 4096) nb = 4096;
     rd_launch(adam_update_kernel, dim3((int)nb), dim3(256), 0, st, *p);
+    return (int)hipGetLastError();
+}
+
+// The guarded optimizer step (train.py --clip_grad_norm / --skip_nonfinite): what stands in front of the reference's
+// `optimizer.step()` (code/train.py:285-287) behind rd_grad_guard (csrc/guard.hip), whose verdict both launches read from the device.
+// The launch geometry is rd_adam_step's.
+int rd_adam_step_guarded(const rd_adam_t* p, const rd_guard_state_t* guard_dev, void* stream) {
+    if (!p || !guard_dev || p->n < 1) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    rd_launch(adam_prepare_guarded_kernel, dim3(1), dim3(1), 0, st, *p, guard_dev);
+    int64_t nb = (p->n + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    rd_launch(adam_update_guarded_kernel, dim3((int)nb), dim3(256), 0, st, *p, guard_dev);
     return (int)hipGetLastError();
 }
 

@@ -166,6 +166,25 @@ class RdAvgRange(C.Structure):
     _fields_ = [('src', vp), ('dst', vp), ('bytes', i64), ('chunk0', i64), ('kind', i32), ('pad_', i32)]
 
 
+GUARD_CHUNK = 16384                                                 # RD_GUARD_CHUNK
+GUARD_MAX_N = 1 << 24                                               # elements rd_grad_guard accepts (rd_step_log's bound)
+
+
+class RdGuardState(C.Structure):
+    """rd_guard_state_t (include/ramdsir.h): the 40 device-resident bytes the guarded step's launches communicate through."""
+    _fields_ = [('norm', f32), ('scale', f32), ('skip', i32), ('nonfinite', i32), ('steps', i64), ('clipped', i64), ('skipped', i64)]
+
+
+class RdGradGuard(C.Structure):
+    """rd_grad_guard_t (include/ramdsir.h): the descriptor of rd_grad_guard."""
+    _fields_ = [('grad', fp), ('n', i64), ('max_norm', f32), ('pad_', i32), ('workspace', vp), ('state', vp)]
+
+
+class RdGuardRange(C.Structure):
+    """rd_guard_range_t (include/ramdsir.h): one live / shadow pair of rd_guard_sync's table."""
+    _fields_ = [('live', vp), ('shadow', vp), ('bytes', i64), ('chunk0', i64)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -251,6 +270,10 @@ _SIGS = {
     'rd_step_log_workspace': (i64, [i64]),
     'rd_snapshot': (C.c_int, [C.POINTER(RdSnapRange), vp, C.c_int, i64, vp, i64, vp, C.c_int, vp]),
     'rd_avg_step': (C.c_int, [C.POINTER(RdAvgRange), vp, C.c_int, i64, vp, C.c_int, f32, i32, vp]),
+    'rd_grad_guard_workspace': (i64, [i64]),
+    'rd_grad_guard': (C.c_int, [C.POINTER(RdGradGuard), vp]),
+    'rd_adam_step_guarded': (C.c_int, [C.POINTER(RdAdam), vp, vp]),
+    'rd_guard_sync': (C.c_int, [C.POINTER(RdGuardRange), vp, C.c_int, i64, vp, vp]),
     'rd_crc32c':(C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),

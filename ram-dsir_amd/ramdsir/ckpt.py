@@ -9,7 +9,9 @@ The file (torch.save of plain containers): format / version, the range table (na
 the blob as one uint8 tensor, the host meta (epoch, iter_num, previous_best, the three host generators, the replay state of every
 cycled loader, the byte length of the validation CSV) and the fingerprint of the run (arguments, geometry, parameter manifest).
 `state_dicts(state)` turns it into the reference's three state_dicts without a GPU.  With train.py --avg_weights the ranges of the
-averaged model ('avg/...', ramdsir/avg.py) follow the trainer's and its settings sit under meta['avg_weights'] (compare_avg_weights).
+averaged model ('avg/...', ramdsir/avg.py) follow the trainer's and its settings sit under meta['avg_weights'] (compare_avg_weights);
+with --clip_grad_norm / --skip_nonfinite the guard's state word ('guard/state', ramdsir/guard.py) follows those and its max_norm sits
+under meta['grad_guard'] (compare_grad_guard).
 
 Checksums of the little-endian uint32 words w[0 .. m) of a range: s1 = sum w[i], s2 = sum (i + 1) w[i], both mod 2^64 (`checksums`
 is the numpy model the kernel equals bit for bit; s2 depends on the order of the words, s1 does not).
@@ -149,6 +151,29 @@ def compare_avg_weights(state, current):
         for k in AVG_SETTINGS:
             if saved.get(k) != current.get(k):
                 raise ValueError('--resume: the snapshot was taken with avg_weights %s = %r, this run has %r' % (k, saved.get(k), current.get(k)))
+
+
+GUARD_PREFIX = 'guard/'         # the state word of the guarded step (ramdsir/guard.py named_ranges)
+GUARD_SETTINGS = ('max_norm',)
+
+
+def compare_grad_guard(state, current):
+    """--resume with / without --clip_grad_norm / --skip_nonfinite.  current: the run's settings (guard.GradGuard.settings()) or None
+    when the guard is off.  ValueError naming grad_guard where the file has no guard state and the run wants one, has one and the run
+    does not, or was taken under another max_norm: the count of skipped steps shapes Adam's bias corrections and cannot be made up or
+    dropped, and a changed clipping norm is another optimizer in the middle of a run."""
+    saved = (state.get('meta') or {}).get('grad_guard')
+    has = any(e['name'].startswith(GUARD_PREFIX) for e in state['table'])
+    if current is not None and not (has and saved):
+        raise ValueError('--resume: the snapshot holds no guard state (it was taken without --clip_grad_norm / --skip_nonfinite); this run '
+                         'has grad_guard = %r' % (dict(current),))
+    if current is None and (has or saved):
+        raise ValueError('--resume: the snapshot holds a guard state (grad_guard = %r); this run was started without --clip_grad_norm / '
+                         '--skip_nonfinite' % ({k: saved.get(k) for k in GUARD_SETTINGS} if saved else None,))
+    if current is not None:
+        for k in GUARD_SETTINGS:
+            if saved.get(k) != current.get(k):
+                raise ValueError('--resume: the snapshot was taken with grad_guard %s = %r, this run has %r' % (k, saved.get(k), current.get(k)))
 
 
 # ------------------------------------------------------------------------------------------------------------- the file

@@ -48,7 +48,9 @@ class GradBuckets:
 
 
 class DataParallelStep:
-    """Wraps a TrainStep: four hipGraphs (segments A, B1, B2, C) with the three all-reduces between them."""
+    """Wraps a TrainStep: four hipGraphs (segments A, B1, B2, C) with the three all-reduces between them.
+    With TrainStep.enable_grad_guard the eager step runs the guarded tail (ramdsir/guard.py) in place of segment C; captured graphs
+    are refused.  No multi-rank run of the guarded step has been made: its test runs a single-rank group."""
 
     def __init__(self, ts, group=None):
         self.ts = ts
@@ -153,6 +155,8 @@ class DataParallelStep:
 
     def capture(self):
         ts = self.ts
+        if ts._guard is not None:
+            raise RuntimeError('DataParallelStep.capture() records segment C: the guarded tail (enable_grad_guard) is not part of it')
         ts._refuse_budgets_on_one_chain('DataParallelStep.capture()')
         ts.wpack.refresh(ts._stream())
         torch.cuda.synchronize()
@@ -195,6 +199,8 @@ class DataParallelStep:
             raise RuntimeError('captured graphs replay the classical step on input slot 0: do not mix them with load_raw_next()')
         if self.graphs is not None and self.ts._after_step is not None:
             raise RuntimeError('captured graphs replay a fixed launch list: nothing can be armed behind their step')
+        if self.graphs is not None and self.ts._guard is not None:
+            raise RuntimeError('captured graphs replay a fixed launch list: the guarded tail cannot replace their segment C')
         # segment -> bucket that is complete when it ends: A -> decoders (2), B1 -> deep encoder (1), B2 -> shallow (0)
         plan = ((0, 2), (1, 1), (2, 0))
         if self.graphs is not None:
@@ -226,7 +232,13 @@ class DataParallelStep:
             if w is not None:
                 w.wait()
         main.wait_stream(self.comm)
-        self._run(3, main)
+        if self.ts._guard is not None:
+            # the guarded tail in place of segment C (ramdsir/guard.py): behind the exchange the gradients are bit-identical on every
+            # rank, so every rank takes the same decision with no collective.  (No multi-rank run of this path has been made: it is
+            # tested on a single-rank group.)
+            self.ts._guard.enqueue_tail(main.cuda_stream)
+        else:
+            self._run(3, main)
         if self.graphs is None:
             self.ts.run_after_step()
             self.ts.advance()

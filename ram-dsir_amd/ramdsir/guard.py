@@ -1,0 +1,221 @@
+"""The guarded optimizer step (train.py --clip_grad_norm / --skip_nonfinite; rd_grad_guard, rd_guard_sync in csrc/guard.hip,
+rd_adam_step_guarded in csrc/loss.hip).  The reference steps on whatever gradient `loss.backward()` leaves (code/train.py:285-287);
+here, on request, the gradient of the whole arena is clipped by its global norm -- all three Adam groups jointly, as
+torch.nn.utils.clip_grad_norm_ over the one optimizer: scale = min(1, max_norm / (norm + 1e-6)) -- and a step whose gradient holds a
+NaN or an infinity, or whose norm is not finite as a float, leaves no trace in the model state: parameters and both moments stay, every
+BatchNorm buffer the forward pass has moved is rolled back, Adam's bias corrections count the updates applied.  The iteration counter
+still advances (the reference's lr is a function of iter_num, code/train.py:289).
+
+Everything is decided on the device: the launches communicate through one 40-byte state word (rd_guard_state_t), every launch argument
+is the same at every step, and the host reads the word only where it synchronises anyway.  The op table of the native launch list is
+ABI, so the guarded tail is NOT part of a launch list: TrainStep.step() ends its native call at the encoder backward with every lane
+joined and enqueues the tail from here, on the main stream.
+
+    GradGuard.enqueue_tail(stream)   rd_grad_guard, rd_adam_step_guarded, the weight repack, rd_guard_sync: six launches
+    GradGuard.read()                 the state word as a dict (synchronises)
+    GradGuard.sync_shadow()          shadow <- live, outside the step (at enable time, after a restore)
+    model(grad, max_norm, state)     the numpy model of rd_grad_guard's two launches, in their summation order
+    GradGuard.named_ranges()         [('guard/state', tensor)] for a training-state snapshot (ramdsir/ckpt.py)
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+CHUNK, THREADS, QUADS = L.LOG_CHUNK, 256, L.LOG_CHUNK // 4 // 256       # rd_grad_guard's first launch (csrc/guard.hip)
+EPS = np.float32(1e-6)
+STATE_FIELDS = tuple(name for name, _ in L.RdGuardState._fields_)
+STATE_BYTES = C.sizeof(L.RdGuardState)
+_LANE = np.arange(64)
+
+
+def workspace_bytes(n):
+    """rd_grad_guard_workspace(n): one {double, int64} pair per chunk."""
+    return -(-max(int(n), 0) // CHUNK) * 16
+
+
+def check_max_norm(max_norm):
+    """max_norm as the kernel receives it (float32): 0 switches clipping off; negative, NaN and infinite values are refused."""
+    m = float(max_norm)
+    if not 0.0 <= m <= float(np.finfo(np.float32).max):             # NaN fails both comparisons
+        raise ValueError('grad guard: max_norm %r (0 for no clipping, or a positive finite number)' % (max_norm,))
+    return m
+
+
+def _lanes_sum(v):
+    """The xor tree over the 64 lanes (last axis) as the kernels run it: offsets 32, 16, ..., 1; every lane ends with the same bits."""
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., _LANE ^ o]
+    return v[..., 0]
+
+
+def _chunk_sums(x, head):
+    """x: float32 [C][len], C chunks of one length; head: words in front of the first 16-byte boundary.  The fp64 sum of squares of
+    each chunk's finite elements in the order of the first launch: per thread the head word, its four quads, the tail word; the
+    64 lanes of each wave in the xor tree; the four waves in ascending order."""
+    Cn, ln = x.shape
+    head = min(head, ln)
+    nq = (ln - head) >> 2
+    tail = head + 4 * nq
+    d = np.where(np.isfinite(x), x, np.float32(0)).astype(np.float64)
+    seq = np.zeros((Cn, THREADS, 2 + 4 * QUADS), np.float64)
+    seq[:, :head, 0] = d[:, :head]
+    quads = np.zeros((Cn, QUADS * THREADS, 4), np.float64)
+    quads[:, :nq] = d[:, head:tail].reshape(Cn, nq, 4)
+    seq[:, :, 1:1 + 4 * QUADS] = quads.reshape(Cn, QUADS, THREADS, 4).transpose(0, 2, 1, 3).reshape(Cn, THREADS, 4 * QUADS)
+    seq[:, :ln - tail, 1 + 4 * QUADS] = d[:, tail:]
+    s = np.zeros((Cn, THREADS), np.float64)
+    for j in range(seq.shape[2]):
+        s = seq[:, :, j] * seq[:, :, j] + s                 # the product of two converted floats is exact in fp64
+    w = _lanes_sum(s.reshape(Cn, THREADS // 64, 64))
+    r = w[:, 0]
+    for k in range(1, THREADS // 64):
+        r = r + w[:, k]
+    return r
+
+
+def partial_sums(grad, align_words=0):
+    """The {sum, count} column pair rd_grad_guard's first launch leaves in its workspace.  align_words: (address of grad / 4) % 4."""
+    g = np.ascontiguousarray(grad, np.float32).reshape(-1)
+    n = g.size
+    head = (-int(align_words)) & 3
+    full = n // CHUNK
+    sums = [_chunk_sums(g[:full * CHUNK].reshape(full, CHUNK), head)] if full else []
+    if n % CHUNK:
+        sums.append(_chunk_sums(g[full * CHUNK:].reshape(1, -1), head))
+    bad = ~np.isfinite(g)
+    chunks = (n + CHUNK - 1) // CHUNK
+    counts = np.add.reduceat(bad.astype(np.int64), np.arange(chunks) * CHUNK)
+    return np.concatenate(sums), counts
+
+
+def scale_of(norm, max_norm):
+    """What a step that is not skipped multiplies its gradient by: min(1, max_norm / (norm + 1e-6)) as separately rounded float32
+    operations; 1 with max_norm 0."""
+    f32 = np.float32
+    if not f32(max_norm) > 0:
+        return f32(1)
+    with np.errstate(all='ignore'):
+        return min(f32(f32(max_norm) / f32(f32(norm) + EPS)), f32(1))
+
+
+def model(grad, max_norm=0.0, state=None, align_words=0):
+    """rd_grad_guard in numpy: the state word after the call, as a dict, from the word before it (None: all zero).  The norm is the
+    float32 of the fp64 square root of the fp64 sum in the kernels' order (lane l of the second launch adds partials l, l + 64, ... in
+    ascending order, then the xor tree); scale is formed from separately rounded float32 operations."""
+    f32 = np.float32
+    sums, counts = partial_sums(grad, align_words)
+    rows = -(-sums.size // 64)
+    padded = np.zeros(rows * 64, np.float64)
+    padded[:sums.size] = sums
+    s = np.zeros(64, np.float64)
+    for row in padded.reshape(rows, 64):
+        s = s + row
+    with np.errstate(all='ignore'):
+        norm = f32(np.sqrt(_lanes_sum(s)))
+    nonfinite = int(counts.sum())
+    skip = nonfinite > 0 or not np.isfinite(norm)
+    scale = f32(1) if skip else scale_of(norm, max_norm)
+    prev = dict.fromkeys(STATE_FIELDS, 0) if state is None else state
+    return dict(norm=float(norm), scale=float(scale), skip=int(skip), nonfinite=nonfinite, steps=int(prev['steps']) + 1,
+                clipped=int(prev['clipped']) + int(scale < 1 and not skip), skipped=int(prev['skipped']) + int(skip))
+
+
+def state_dict_of(raw):
+    """40 bytes (bytes, or a uint8 / int64 array) -> the fields of rd_guard_state_t as Python numbers."""
+    raw = bytes(raw) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).tobytes()
+    s = L.RdGuardState.from_buffer_copy(raw[:STATE_BYTES])
+    return {k: getattr(s, k) for k in STATE_FIELDS}
+
+
+def bank_ranges(bank, shadows):
+    """[(name, live tensor, shadow tensor)]: every BatchNorm buffer of the bank -- running_mean, running_var and the int64
+    num_batches_tracked of all three modules -- in the bank's order.  The roll-back is a byte copy: the dtype does not matter."""
+    return [('guard/shadow/%s/%s' % (m, key), t, shadows[(m, key)]) for (m, key), t in bank.buffers.items()]
+
+
+def build_table(entries):
+    """[(live pointer, shadow pointer, bytes)] -> (the rd_guard_range_t array with its chunk0 column filled in, total chunks)."""
+    arr, chunks = (L.RdGuardRange * max(len(entries), 1))(), 0
+    for e, (live, shadow, nbytes) in zip(arr, entries):
+        e.live, e.shadow, e.bytes, e.chunk0 = live, shadow, nbytes, chunks
+        chunks += (max(nbytes, 0) + L.GUARD_CHUNK - 1) // L.GUARD_CHUNK
+    return arr, chunks
+
+
+def upload_table(arr, n, device):
+    return torch.from_numpy(np.frombuffer(bytes(arr), np.uint8)[:max(n, 1) * C.sizeof(L.RdGuardRange)].copy()).to(device)
+
+
+def run_guard(desc, stream=None):
+    """One rd_grad_guard call; returns its code (0, or the negative validation code: nothing was launched)."""
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    return L.lib().rd_grad_guard(C.byref(desc) if desc is not None else None, s)
+
+
+def run_sync(arr, table_dev, n, chunks, state_ptr, stream=None):
+    """One rd_guard_sync call; returns its code."""
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    return L.lib().rd_guard_sync(arr, table_dev.data_ptr() if table_dev is not None else None, n, chunks, state_ptr, s)
+
+
+class GradGuard:
+    """The state word, the workspace, the shadow copies of the BatchNorm buffers with their range table, and the guarded tail of a
+    FusedTrainer's step.  max_norm 0: the guard without clipping (--skip_nonfinite alone).  An active guard always skips non-finite
+    steps.  Data parallel: the gradients are bit-identical on every rank behind the exchange, so every rank takes the same decision
+    without a collective; the shadows are rank-local like the buffers they copy."""
+
+    def __init__(self, trainer, max_norm=0.0):
+        self.trainer, self.max_norm = trainer, check_max_norm(max_norm)
+        self.bank, self.ts = bank, ts = trainer.bank, trainer.ts
+        if bank.n > L.GUARD_MAX_N:
+            raise ValueError('grad guard: an arena of %d elements (rd_grad_guard takes up to %d)' % (bank.n, L.GUARD_MAX_N))
+        dev = bank.device
+        self.state = torch.zeros(STATE_BYTES // 8, dtype=torch.int64, device=dev)
+        self.workspace = torch.empty(workspace_bytes(bank.n) // 8, dtype=torch.float64, device=dev)
+        d = L.RdGradGuard()
+        d.grad, d.n, d.max_norm = bank.grads.data_ptr(), bank.n, self.max_norm
+        d.workspace, d.state = self.workspace.data_ptr(), self.state.data_ptr()
+        self.desc = d
+        self.shadows = {k: t.detach().clone() for k, t in bank.buffers.items()}
+        self.ranges = bank_ranges(bank, self.shadows)
+        for name, a, b in self.ranges:
+            nbytes = a.numel() * a.element_size()
+            if nbytes % 4 or not (a.is_contiguous() and b.is_contiguous()):
+                raise ValueError('range %s: %d bytes of a %s tensor (a contiguous multiple of 4 bytes is needed)' % (name, nbytes, a.dtype))
+        self.n = len(self.ranges)
+        self.arr, self.chunks = build_table([(a.data_ptr(), b.data_ptr(), a.numel() * a.element_size()) for _, a, b in self.ranges])
+        self.table_dev = upload_table(self.arr, self.n, dev)            # once: the pointers never move
+
+    def settings(self):
+        """What a snapshot records and --resume compares."""
+        return dict(max_norm=self.max_norm)
+
+    def sync_shadow(self):
+        """shadow <- live outside the step: the buffers as they are become what a skipped step rolls back to."""
+        for _, live, shadow in self.ranges:
+            shadow.copy_(live)
+
+    def enqueue_tail(self, stream):
+        """The step's tail behind whatever `stream` holds (the encoder backward, every lane joined): the verdict, Adam under it, the
+        weight repack (of unchanged parameters behind a skipped step), the roll-back or the refresh of the shadows."""
+        lib, st = L.lib(), self.state.data_ptr()
+        L.check(lib.rd_grad_guard(C.byref(self.desc), stream), 'rd_grad_guard')
+        L.check(lib.rd_adam_step_guarded(C.byref(self.ts.ad), st, stream), 'rd_adam_step_guarded')
+        self.ts.wpack.refresh(stream)
+        L.check(lib.rd_guard_sync(self.arr, self.table_dev.data_ptr(), self.n, self.chunks, st, stream), 'rd_guard_sync')
+
+    def read(self):
+        """The state word as a dict: norm, scale, skip, nonfinite of the last step; steps, clipped, skipped so far.  Synchronises."""
+        return state_dict_of(self.state.cpu().numpy())
+
+    def model(self, grad, state=None):
+        """model() with this object's max_norm and the alignment of the trainer's gradient arena."""
+        return model(grad, self.max_norm, state, align_words=(self.bank.grads.data_ptr() >> 2) & 3)
+
+    def named_ranges(self):
+        """[(name, tensor)] for ckpt.TrainState's extra ranges: the state word, whose `skipped` count Adam's bias corrections depend on.
+        The shadows are not state: behind a completed step they equal the live buffers (sync_shadow() after a restore)."""
+        return [('guard/state', self.state)]

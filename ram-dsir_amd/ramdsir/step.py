@@ -135,6 +135,7 @@ class TrainStep:
         self.launch_threads = int(opt['launch_threads']) > 0 and self.fork      # (-1: DataParallelStep measures it; one process: one thread)
         self._slot1_keep = []
         self._after_step = None
+        self._guard = None
         self._ops = self._build_ops()
 
     def _build_ops(self):
@@ -400,6 +401,8 @@ class TrainStep:
 
     def capture(self):
         """Capture one step (zeroing + every launch) into a hipGraph on a side stream."""
+        if self._guard is not None:
+            raise RuntimeError('capture() records the classical step: the guarded tail (enable_grad_guard) is not part of a launch list')
         self._refuse_budgets_on_one_chain('capture()')
         self.wpack.refresh(self._stream())
         torch.cuda.synchronize()
@@ -449,9 +452,22 @@ class TrainStep:
                 raise RuntimeError('a captured hipGraph replays a fixed launch list: nothing can be armed behind its step')
             self.graph.replay()
             return
-        self.launch(self.head_names() + self.backward_names() + ('seg_c',), join_before_last=True)
+        if self._guard is not None:
+            # the guarded tail is not in the op table of the launch list: the native call ends at the encoder backward with every
+            # lane joined, and Adam + repack follow as direct calls on the main stream (ramdsir/guard.py)
+            self.launch(self.head_names() + self.backward_names(), join=True)
+            self._guard.enqueue_tail(torch.cuda.current_stream().cuda_stream)
+        else:
+            self.launch(self.head_names() + self.backward_names() + ('seg_c',), join_before_last=True)
         self.run_after_step()
         self.advance()
+
+    def enable_grad_guard(self, guard):
+        """From now on step() runs guard.enqueue_tail (rd_grad_guard, rd_adam_step_guarded, the repack, rd_guard_sync) in place of
+        seg_c.  A captured hipGraph replays a fixed launch list: refused."""
+        if self.graph is not None:
+            raise RuntimeError('a captured hipGraph replays a fixed launch list: the guarded tail cannot replace its Adam')
+        self._guard = guard
 
     def loss_dict(self):
         """Synchronises.  Names follow the tensorboard scalars of train.py:298-304."""

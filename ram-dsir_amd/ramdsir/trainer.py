@@ -28,7 +28,7 @@ class FusedTrainer:
                               options=dict(side_cus=0, rec_cus=0) if use_graph else None)
         self.ts.wpack.refresh()
         self._primed, self._graphs, self._announced = False, bool(use_graph), None
-        self._tb, self._tb_pending, self._tb_hook, self._log, self._avg = None, None, None, None, None
+        self._tb, self._tb_pending, self._tb_hook, self._log, self._avg, self._guard = None, None, None, None, None, None
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -118,6 +118,20 @@ class FusedTrainer:
         from . import avg
         self._avg = avg.WeightAverage(self, mode, decay, start)
         return self._avg
+
+    def enable_grad_guard(self, max_norm=0.0):
+        """From now on every step() runs the guarded tail (ramdsir/guard.py) in place of Adam + repack: the global gradient norm of the
+        whole arena, Adam on the gradient scaled by min(1, max_norm / (norm + 1e-6)) (max_norm 0: no clipping), and a step whose
+        gradient is not finite leaves parameters, moments and every BatchNorm buffer as they were (the shadow copies are initialised
+        HERE from the live buffers).  Decided on the device, no read-back.  The after-step launches (step log, averaging, image grids)
+        run behind the guarded tail as behind Adam; the gradient arena is never modified.  Returns the guard.GradGuard.  Not with
+        use_graph=True."""
+        if self._graphs:
+            raise RuntimeError('enable_grad_guard: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        from . import guard
+        self._guard = guard.GradGuard(self, max_norm)
+        self.ts.enable_grad_guard(self._guard)
+        return self._guard
 
     def enable_step_log(self, health=False, rows=256):
         """From now on every step() appends one row to a device-resident ring (ramdsir/step_log.py, rd_step_log): the losses, the lr and

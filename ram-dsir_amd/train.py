@@ -20,7 +20,10 @@ continues from such a file -- bit-identically with --gpu_data or --num_workers 0
 (ramdsir/ckpt.py); the reference can only start from a fresh initialisation; (vi) --avg_weights ema | uniform keeps a second copy of
 the model, averaged along the trajectory by one HIP launch behind every step (ramdsir/avg.py, rd_avg_step), validates it beside the live
 one where --fused_val is in use (<target>_val_log_avg.csv, model_avg_%.2f.pth) and writes final_model_avg.pth; the reference keeps the
-last iterate only.
+last iterate only; (vii) --clip_grad_norm X clips the gradient of the whole model by its global norm in front of Adam and
+--skip_nonfinite makes a step with a non-finite gradient leave no trace in the model state (parameters, moments, BatchNorm buffers),
+both decided on the device (ramdsir/guard.py: rd_grad_guard, rd_adam_step_guarded, rd_guard_sync); the reference steps on whatever
+gradient it gets (code/train.py:285-287).
 """
 import argparse
 import os
@@ -139,6 +142,14 @@ def parse_args(argv=None):
     p.add_argument('--avg_start', type=int, default=None, metavar='ITER',
                    help='--avg_weights: the iteration from which on iterates are averaged; until then the averaged model is a copy of the '
                         'live one; default 0')
+    p.add_argument('--clip_grad_norm', type=float, default=None, metavar='X',
+                   help='before Adam, scale the gradient of the whole model (all three parameter groups jointly, as '
+                        'torch.nn.utils.clip_grad_norm_ over the one optimizer) by min(1, X / (norm + 1e-6)); X > 0 and finite; decided on '
+                        'the device in HIP (ramdsir/guard.py), no read-back; implies --skip_nonfinite; --norm bn only; off by default')
+    p.add_argument('--skip_nonfinite', action='store_true',
+                   help='a step whose gradient holds a NaN or an infinity, or whose norm is not finite, leaves no trace in the model: '
+                        'parameters and Adam moments stay, every BatchNorm buffer is rolled back, the bias corrections count the updates '
+                        'applied; the iteration counter (and with it the lr schedule) still advances; --norm bn only; off by default')
     return p.parse_args(argv)
 
 
@@ -439,6 +450,29 @@ def avg_settings(args):
     return args.avg_weights, AVG_DECAY if args.avg_decay is None else args.avg_decay, 0 if args.avg_start is None else args.avg_start
 
 
+def uses_guard(args):
+    """Either flag turns the guarded optimizer step on (ramdsir/guard.py); without both the step is the unguarded one, launch for
+    launch."""
+    return bool(args.clip_grad_norm is not None or args.skip_nonfinite)
+
+
+def guard_max_norm(args):
+    """The guard's max_norm: --clip_grad_norm, or 0 (no clipping) for --skip_nonfinite alone."""
+    return 0.0 if args.clip_grad_norm is None else float(args.clip_grad_norm)
+
+
+GUARD_TAGS = ('guard/grad_norm', 'guard/scale', 'guard/clipped', 'guard/skipped')
+
+
+def guard_pairs(g):
+    """The four scalars of a logging iteration from the guard's state word: norm and scale of that iteration's step, the counts so far."""
+    return list(zip(GUARD_TAGS, (g['norm'], g['scale'], float(g['clipped']), float(g['skipped']))))
+
+
+def guard_suffix(g):
+    return ' grad_norm %.4g scale %.4g clipped %d skipped %d' % (g['norm'], g['scale'], g['clipped'], g['skipped'])
+
+
 def val_log_path(args, suffix=''):
     return osp.join(args.save_path, str(args.test_domain_idx) + '_val_log%s.csv' % suffix)
 
@@ -509,14 +543,23 @@ def check_args(args, world):
         raise ValueError('--avg_decay takes a decay in (0, 1), got %r' % args.avg_decay)
     if args.avg_start is not None and args.avg_start < 0:
         raise ValueError('--avg_start takes an iteration number, got %d' % args.avg_start)
+    # (the kernel receives the norm as float32: a value that is infinite there is refused with the ones that are infinite as given)
+    if args.clip_grad_norm is not None and not 0.0 < args.clip_grad_norm <= float(np.finfo(np.float32).max):      # NaN fails both
+        raise ValueError('--clip_grad_norm takes a positive finite norm, got %r' % args.clip_grad_norm)
+    if uses_guard(args) and args.norm != 'bn':
+        raise ValueError('--clip_grad_norm / --skip_nonfinite guard the fused step\'s Adam launch: --norm %s trains through the modules, '
+                         'whose Adam is torch\'s' % args.norm)
 
 
 class TrainLog:
     """The logging side of the loop: the event file in <save_path>/log (train.py:538) and the console lines of rank 0, and --
     on every rank, because the drain is collective -- the reads of the per-step device ring (--tb_every_iter / --tb_health)."""
 
-    def __init__(self, args, trainer, rank, imgs_per_iter):
+    def __init__(self, args, trainer, rank, imgs_per_iter, guard=None):
         self.args, self.trainer, self.rank0, self.imgs_per_iter = args, trainer, rank == 0, imgs_per_iter
+        # --clip_grad_norm / --skip_nonfinite: the guard's state word is read at the logging iterations, behind the read of the losses
+        self.guard = guard
+        self.guard_mark = guard.read() if guard is not None else None      # (behind a --resume restore: the counts continue)
         # --tb_images: one writer thread owns the event file (scalars go through its queue too, so the records keep the order of the
         # calls); without the flag the direct writer, record for record what it always wrote
         Writer = QueuedWriter if args.tb_images else SummaryWriter
@@ -541,6 +584,20 @@ class TrainLog:
                       'continues' % (rec['iteration'], rec['nonfinite'], rec['losses']['loss']))
         return records
 
+    def guard_report(self, iter_num):
+        """A logging iteration with the guard on: (the console line's suffix, the four guard/* scalars) from the state word -- read
+        behind the read of the losses, which has synchronised already.  Warns when every step since the previous logging iteration
+        was skipped.  Without the guard: ('', [])."""
+        if self.guard is None:
+            return '', []
+        g, mark = self.guard.read(), self.guard_mark
+        self.guard_mark = g
+        steps, skipped = g['steps'] - mark['steps'], g['skipped'] - mark['skipped']
+        if steps > 0 and skipped == steps:
+            print('grad_guard: warning: every one of the %d steps up to iteration %d was skipped (non-finite gradients); the model has '
+                  'not moved since iteration %d' % (steps, iter_num, iter_num - steps))
+        return guard_suffix(g), guard_pairs(g)
+
     def after_step(self, iter_num, log_images):
         """Behind the step of iteration iter_num.  With the ring, it is read where the loop synchronises anyway (the logging
         iterations), in front of image records (they follow the scalars of their own iteration) and when it is full -- all
@@ -551,14 +608,18 @@ class TrainLog:
             if log_now or (args.tb_images > 0 and iter_num % args.tb_images == 0) or trainer.step_log_full():
                 records = self.drain()
                 if self.rank0 and log_now:                  # printed and written from the same drained row
-                    print(console_line(iter_num, records[-1]['lr'], records[-1]['losses']))
+                    suffix, pairs = self.guard_report(iter_num)
+                    print(console_line(iter_num, records[-1]['lr'], records[-1]['losses']) + suffix)
+                    if pairs:
+                        self.writer.add_scalars_at(iter_num, pairs)
         elif log_now:
             l = trainer.losses()                            # collective when world > 1: the mean over the ranks
             if self.rank0:
                 lr_now = trainer.lr()
-                print(console_line(iter_num, lr_now, l))
+                suffix, pairs = self.guard_report(iter_num)
+                print(console_line(iter_num, lr_now, l) + suffix)
                 # the reference's scalars (train.py:298-304 / 467-473), at the iterations whose losses are read back
-                self.writer.add_scalars_at(iter_num, scalar_pairs(lr_now, l))
+                self.writer.add_scalars_at(iter_num, scalar_pairs(lr_now, l) + pairs)
         if log_images:                                      # behind the scalars of the iteration, in the reference's tag order
             self.writer.add_images_at(iter_num, trainer.take_tb_images())
         if iter_num + 1 == 5:                               # end-to-end throughput (files -> DataLoader -> H2D -> step), start-up excluded
@@ -670,16 +731,22 @@ def init_process(world, local):
     return dist.new_group(backend='gloo') if world > 1 else None
 
 
-def open_state(args, trainer, fingerprint_args, resume_state, avg=None):
+def open_state(args, trainer, fingerprint_args, resume_state, avg=None, guard=None):
     """--ckpt_every / --resume, device side: the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py);
     --resume: the arenas, the BatchNorm buffers and the schedule counter from the file (restore_host_side follows before the loop).
-    avg (--avg_weights): the averaged model's ranges go behind the trainer's; a file and a run that disagree about them are refused."""
+    avg (--avg_weights): the averaged model's ranges go behind the trainer's; a file and a run that disagree about them are refused.
+    guard (--clip_grad_norm / --skip_nonfinite): its state word goes behind those, under the same rule; behind a restore its shadow
+    copies are taken from the restored BatchNorm buffers."""
     from ramdsir import ckpt
     if resume_state is not None:
         ckpt.compare_avg_weights(resume_state, avg.settings() if avg is not None else None)
-    state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, *fingerprint_args), extra=avg.named_ranges() if avg is not None else None)
+        ckpt.compare_grad_guard(resume_state, guard.settings() if guard is not None else None)
+    extra = (avg.named_ranges() if avg is not None else []) + (guard.named_ranges() if guard is not None else [])
+    state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, *fingerprint_args), extra=extra or None)
     if resume_state is not None:
         state_io.restore(resume_state)
+        if guard is not None:
+            guard.sync_shadow()
     if not args.gpu_data and args.num_workers > 0:
         print('ckpt: model, optimizer and schedule state are restored exactly; with DataLoader worker processes the draws come from '
               'freshly seeded workers (use --gpu_data or --num_workers 0 for a bit-identical continuation)')
@@ -748,13 +815,15 @@ def main(args):
     modules, trainer, (H, W), total_iters = build_trainer(args, rank, raw, resident, bsl, max_len)
     # --avg_weights: the second bank, a copy of the initial model (rank-local under data parallelism, as the BatchNorm buffers are)
     avg = trainer.enable_avg_weights(*avg_settings(args)) if uses_avg(args) else None
-    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg) if uses_ckpt(args) else None
+    # --clip_grad_norm / --skip_nonfinite: the guarded tail replaces Adam + repack in the step; the shadows copy the initial buffers
+    guard = trainer.enable_grad_guard(guard_max_norm(args)) if uses_guard(args) else None
+    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg, guard) if uses_ckpt(args) else None
     if val is not None:
         val.bind(trainer)
         if avg is not None and val.mode != 'fused':
             print('avg_weights: the averaged model is maintained and written at the end, but not validated per epoch (that pass is the '
                   'fused forward of --gpu_val / --gpu_val_volumes with --fused_val)')
-    log = TrainLog(args, trainer, rank, world * sum(bsl))
+    log = TrainLog(args, trainer, rank, world * sum(bsl), guard)
     previous_best, iter_num, start_epoch, previous_best_avg = 0.0, 0, 0, 0.0
     if resume_state is not None:
         start_epoch, iter_num, previous_best = restore_host_side(args, resume_state['meta'], loaders, raw)
@@ -801,6 +870,8 @@ def main(args):
                 avg_log = val_log_path(args, '_avg')
                 meta['avg_weights'] = dict(avg.settings(), previous_best_avg=previous_best_avg,
                                            val_log_bytes=os.path.getsize(avg_log) if os.path.exists(avg_log) else 0)
+            if guard is not None:
+                meta['grad_guard'] = guard.settings()
             state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), meta)
         if rank == 0:
             t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * log.imgs_per_iter
@@ -814,6 +885,9 @@ def main(args):
             break
     if log.step_log:
         log.drain()                                         # the rows behind the last logging iteration
+    if guard is not None and rank == 0:
+        g = guard.read()
+        print('grad_guard: %d of %d steps clipped, %d skipped' % (g['clipped'], g['steps'], g['skipped']))
     if state_io is not None:
         state_io.close()                                    # the last snapshot is durable
         if state_io.seconds['calls']:
