@@ -912,6 +912,68 @@ int rd_adam_step_guarded(const rd_adam_t* p, const rd_guard_state_t* guard_dev, 
 int rd_guard_sync(const rd_guard_range_t* table_host, const rd_guard_range_t* table_dev, int n, int64_t total_chunks,
                   const rd_guard_state_t* guard_dev, void* stream);
 
+/* Grouped Adam (train.py --weight_decay / --wd_mode / --lr_schedule / --warmup_iters / --enc_lr_mult, ramdsir/optim.py),
+ * csrc/optim.hip: torch's param_groups as a device table of contiguous ranges of the arena, each with its own learning-rate
+ * multiplier and weight decay, and a schedule chosen by a field and evaluated on the device from the iteration counter.  The
+ * reference's optimizer (code/train.py:573-576, 289-293; rd_adam_step) is the special case schedule poly, no warm-up and the table
+ * {[0, n_half_lr): 0.5, 0}, {[n_half_lr, n): 1, 0}: with it rd_optim_step leaves the bits rd_adam_step leaves (guard_dev null) or
+ * rd_adam_step_guarded leaves (guard_dev set), for any values, non-finite ones included -- the three update kernels share ONE source
+ * text of the per-element arithmetic (csrc/adam_body.h).
+ *
+ * The table: n_ranges <= 4096 entries {first, count, lr_mult, weight_decay, chunk0}, sorted, contiguous, covering [0, n) exactly,
+ * count >= 1.  Range starts have any 4-byte alignment (the arena packs tensors back to back).  Work decomposition: rd_avg_step's --
+ * range i is cut into chunks of RD_OPT_CHUNK ELEMENTS from its start (the last one ragged, a chunk never straddles two ranges),
+ * chunk0 = the number of chunks of the ranges in front of it, the grid is flat over all chunks (not capped), a workgroup finds its
+ * range by a search over the chunk0 column of the device table (one load per thread and a count over the workgroup, behind binary
+ * steps only above 256 ranges) -- per workgroup, never per element -- and moves the part of its
+ * chunk that starts at a 16-byte boundary of all four arenas with 16-byte accesses, the words in front of and behind it one by one.
+ *
+ * Two launches.  (1) prepare, one thread, all in fp64, each word rounded once to fp32: with it = *iter,
+ *     s(it) = schedule 0 (poly):     it == 0 ? 1 : (1 - (it - 1) / total_iters) ^ 0.9      rd_adam_step's expression, the reference's
+ *                                                                                            one-iteration lag included
+ *             schedule 1 (cosine):   0.5 * (1 + cos(pi * min(it, total_iters) / total_iters))      no lag
+ *             schedule 2 (constant): 1
+ *     w(it) = warmup_iters > 0 ? min(1, (it + 1) / warmup_iters) : 1
+ *     hyper_out[0] = (float)(base_lr * s * w);  hyper_out[1..3] and *iter += 1 as rd_adam_step; with guard_dev the bias
+ *     corrections count the updates applied, t = max(1, it + 1 - guard->skipped), as rd_adam_step_guarded.
+ * (2) update: for element i of a range with multiplier M and decay D, separately rounded fp32 operations:
+ *     lr_g = M * hyper_out[0]                                 (M = 0.5 and M = 1 give the bits of rd_adam_step's two rates)
+ *     g = grad[i];  with guard_dev: nothing at all is stored when guard->skip is set, otherwise g = g * guard->scale
+ *     D > 0, wd_mode 0 (decoupled):  param[i] = param[i] * (1 - lr_g * D)     torch.optim.AdamW's param.mul_(1 - lr * wd), first
+ *     D > 0, wd_mode 1 (L2):         g = fma(D, param[i], g)                  torch.optim.Adam(weight_decay), behind the guard's
+ *                                                                             scale as clip_grad_norm_ precedes optimizer.step()
+ *     D == 0: neither operation is executed;  then rd_adam_step's update of exp_avg[i], exp_avg_sq[i], param[i] at rate lr_g.
+ * ramdsir/optim.py schedule_model / decay_model are the same arithmetic in numpy.
+ *
+ * Returns, before anything is launched: -1 a null descriptor / arena / iter / hyper_out / table, n < 1 or n_ranges outside
+ * 1..4096; -4 an unknown schedule or wd_mode, warmup_iters < 0 or >= total_iters; -2 a range with count < 1, ranges that are not
+ * contiguous or do not cover [0, n); -3 an lr_mult that is not finite or <= 0, a weight_decay that is negative or not finite; -5 a
+ * chunk0 column or total_chunks that does not match the counts.  Nothing is allocated, synchronised or copied; both launches go
+ * through the library's one launch site.  rd_adam_t, rd_adam_step and rd_adam_step_guarded are unchanged. */
+#define RD_OPT_CHUNK 4096
+#define RD_OPT_MAX_RANGES 4096
+typedef struct {
+    float* param; const float* grad; float* exp_avg; float* exp_avg_sq;     /* device arenas */
+    int64_t n;              /* total elements */
+    int32_t* iter;          /* device, incremented */
+    float* hyper_out;       /* device [4]: rd_adam_step's layout */
+    float base_lr;
+    int32_t total_iters;
+    float beta1, beta2, eps;
+    int32_t schedule;       /* 0 poly, 1 cosine, 2 constant */
+    int32_t warmup_iters;   /* 0: none */
+    int32_t wd_mode;        /* 0 decoupled (AdamW), 1 L2 (Adam(weight_decay)) */
+} rd_optim_t;
+typedef struct {
+    int64_t first;          /* first element of the range in the arena */
+    int64_t count;          /* elements, >= 1 */
+    float lr_mult;          /* the range's rate is lr_mult * hyper_out[0] */
+    float weight_decay;     /* 0: none */
+    int64_t chunk0;         /* first chunk of the range in the flat grid */
+} rd_optim_range_t;
+int rd_optim_step(const rd_optim_t* p, const rd_optim_range_t* table_host, const rd_optim_range_t* table_dev, int n_ranges,
+                  int64_t total_chunks, const rd_guard_state_t* guard_dev /* may be NULL */, void* stream);
+
 /* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
  * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
  * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */

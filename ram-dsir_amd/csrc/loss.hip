@@ -4,6 +4,7 @@
 // code/utils/losses.py:8-33 (dice_loss, dice_loss_multi), torch.nn.BCELoss / CrossEntropyLoss /
 // MSELoss / KLDivLoss semantics, torch.optim.Adam + poly LR code/train.py:573-576,289-293.
 #include "common.h"
+#include "adam_body.h"
 #include "../../include/ramdsir.h"
 
 namespace {
@@ -361,12 +362,8 @@ __device__ __forceinline__ void adam_prepare(const rd_adam_t& p, int it, long lo
     // LR in force at iteration `it` was written after iteration it-1 from ITS iter_num (train.py:289)
     double lr = p.base_lr;
     if (it > 0) lr = (double)p.base_lr * pow(1.0 - (double)(it - 1) / (double)p.total_iters, 0.9);
-    const double t = (double)(applied + 1);
     p.hyper_out[0] = (float)lr;
-    p.hyper_out[1] = (float)(1.0 - pow((double)p.beta1, t));
-    p.hyper_out[2] = (float)(1.0 - pow((double)p.beta2, t));
-    p.hyper_out[3] = (float)it;
-    *p.iter = it + 1;
+    adam_prepare_words(p.hyper_out, p.iter, p.beta1, p.beta2, it, applied);
 }
 
 __global__ void adam_prepare_kernel(const rd_adam_t p) {
@@ -382,7 +379,7 @@ __global__ void adam_prepare_guarded_kernel(const rd_adam_t p, const rd_guard_st
     adam_prepare(p, it, applied > 0 ? applied : 0);
 }
 
-// ONE body for both update kernels.  GUARDED = false is rd_adam_step's kernel as it always was (scale is not read);
+// ONE body for both update kernels (its per-element arithmetic is adam_element, adam_body.h, which rd_optim_step shares).  GUARDED = false is rd_adam_step's kernel as it always was (scale is not read);
 // GUARDED = true multiplies the gradient by the guard's scale first: one rounded fp32 product, then the same expressions.
 // The grid-stride bounds are formed in the kernels: read there, the launch geometry comes from scalar loads of the kernel's own
 // arguments, as it did in rd_adam_step's kernel before the body was shared.
@@ -392,13 +389,7 @@ __device__ __forceinline__ void adam_update(const rd_adam_t& p, float scale, int
     const float sq_bc2 = sqrtf(bc2);
     for (int64_t i = first; i < p.n; i += stride) {
         const float g = GUARDED ? __fmul_rn(p.grad[i], scale) : p.grad[i];
-        const float m = p.beta1 * p.exp_avg[i] + (1.f - p.beta1) * g;
-        const float v = p.beta2 * p.exp_avg_sq[i] + (1.f - p.beta2) * g * g;
-        p.exp_avg[i] = m;
-        p.exp_avg_sq[i] = v;
-        const float step = (i < p.n_half_lr ? 0.5f * lr : lr) / bc1;
-        const float denom = sqrtf(v) / sq_bc2 + p.eps;
-        p.param[i] -= step * (m / denom);
+        adam_element(p.param[i], p.exp_avg[i], p.exp_avg_sq[i], g, i < p.n_half_lr ? 0.5f * lr : lr, bc1, sq_bc2, p.beta1, p.beta2, p.eps);
     }
 }
 

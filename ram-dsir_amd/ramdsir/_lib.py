@@ -185,6 +185,24 @@ class RdGuardRange(C.Structure):
     _fields_ = [('live', vp), ('shadow', vp), ('bytes', i64), ('chunk0', i64)]
 
 
+OPT_CHUNK = 4096                                                    # RD_OPT_CHUNK (elements)
+OPT_MAX_RANGES = 4096                                               # RD_OPT_MAX_RANGES
+OPT_POLY, OPT_COSINE, OPT_CONSTANT = 0, 1, 2                        # rd_optim_t.schedule
+OPT_DECOUPLED, OPT_L2 = 0, 1                                        # rd_optim_t.wd_mode
+
+
+class RdOptim(C.Structure):
+    """rd_optim_t (include/ramdsir.h): the descriptor of rd_optim_step -- rd_adam_t without n_half_lr, with the schedule fields."""
+    _fields_ = [('param', fp), ('grad', fp), ('exp_avg', fp), ('exp_avg_sq', fp), ('n', i64), ('iter', vp), ('hyper_out', fp),
+                ('base_lr', f32), ('total_iters', i32), ('beta1', f32), ('beta2', f32), ('eps', f32), ('schedule', i32),
+                ('warmup_iters', i32), ('wd_mode', i32)]
+
+
+class RdOptimRange(C.Structure):
+    """rd_optim_range_t (include/ramdsir.h): one param group of rd_optim_step's table, a contiguous range of the arena."""
+    _fields_ = [('first', i64), ('count', i64), ('lr_mult', f32), ('weight_decay', f32), ('chunk0', i64)]
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -274,6 +292,7 @@ _SIGS = {
     'rd_grad_guard': (C.c_int, [C.POINTER(RdGradGuard), vp]),
     'rd_adam_step_guarded': (C.c_int, [C.POINTER(RdAdam), vp, vp]),
     'rd_guard_sync': (C.c_int, [C.POINTER(RdGuardRange), vp, C.c_int, i64, vp, vp]),
+    'rd_optim_step': (C.c_int, [C.POINTER(RdOptim), C.POINTER(RdOptimRange), vp, C.c_int, i64, vp, vp]),
     'rd_crc32c':(C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),

@@ -11,7 +11,9 @@ cycled loader, the byte length of the validation CSV) and the fingerprint of the
 `state_dicts(state)` turns it into the reference's three state_dicts without a GPU.  With train.py --avg_weights the ranges of the
 averaged model ('avg/...', ramdsir/avg.py) follow the trainer's and its settings sit under meta['avg_weights'] (compare_avg_weights);
 with --clip_grad_norm / --skip_nonfinite the guard's state word ('guard/state', ramdsir/guard.py) follows those and its max_norm sits
-under meta['grad_guard'] (compare_grad_guard).
+under meta['grad_guard'] (compare_grad_guard); the settings of the grouped Adam (--weight_decay, --wd_mode, --lr_schedule,
+--warmup_iters, --enc_lr_mult; ramdsir/optim.py) sit under meta['optim'] (compare_optim) -- it adds no range: its state is the
+arenas, the counter and the schedule words.
 
 Checksums of the little-endian uint32 words w[0 .. m) of a range: s1 = sum w[i], s2 = sum (i + 1) w[i], both mod 2^64 (`checksums`
 is the numpy model the kernel equals bit for bit; s2 depends on the order of the words, s1 does not).
@@ -28,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .optim import DEFAULTS as OPTIM_DEFAULTS               # the reference's optimizer: what a file without the record was taken under
 
 FORMAT, VERSION = 'ramdsir-train-state', 1
 SUM_BYTES = 8 * L.SNAP_SUM_STRIDE         # of the sums buffer per range
@@ -174,6 +177,18 @@ def compare_grad_guard(state, current):
         for k in GUARD_SETTINGS:
             if saved.get(k) != current.get(k):
                 raise ValueError('--resume: the snapshot was taken with grad_guard %s = %r, this run has %r' % (k, saved.get(k), current.get(k)))
+
+
+def compare_optim(state, current):
+    """--resume with / without the optimizer flags (--weight_decay, --wd_mode, --lr_schedule, --warmup_iters, --enc_lr_mult).
+    current: the run's settings (optim.GroupedAdam.settings()) or None when every flag has its default.  The settings travel under
+    meta['optim']; a file without the record was taken under the defaults and resumes only under them.  ValueError naming the first
+    field in which file and run differ: another decay, schedule or multiplier is another optimizer in the middle of a run."""
+    saved = dict(OPTIM_DEFAULTS, **((state.get('meta') or {}).get('optim') or {}))
+    now = dict(OPTIM_DEFAULTS, **(current or {}))
+    for k in OPTIM_DEFAULTS:
+        if saved[k] != now[k]:
+            raise ValueError('--resume: the snapshot was taken with optim %s = %r, this run has %r' % (k, saved[k], now[k]))
 
 
 # ------------------------------------------------------------------------------------------------------------- the file

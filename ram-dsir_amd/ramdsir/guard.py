@@ -11,7 +11,8 @@ is the same at every step, and the host reads the word only where it synchronise
 ABI, so the guarded tail is NOT part of a launch list: TrainStep.step() ends its native call at the encoder backward with every lane
 joined and enqueues the tail from here, on the main stream.
 
-    GradGuard.enqueue_tail(stream)   rd_grad_guard, rd_adam_step_guarded, the weight repack, rd_guard_sync: six launches
+    GradGuard.enqueue_tail(stream)   rd_grad_guard, rd_adam_step_guarded (rd_optim_step with the state word where the trainer's
+                                     grouped Adam is enabled, ramdsir/optim.py), the weight repack, rd_guard_sync: six launches
     GradGuard.read()                 the state word as a dict (synchronises)
     GradGuard.sync_shadow()          shadow <- live, outside the step (at enable time, after a restore)
     model(grad, max_norm, state)     the numpy model of rd_grad_guard's two launches, in their summation order
@@ -203,7 +204,10 @@ class GradGuard:
         weight repack (of unchanged parameters behind a skipped step), the roll-back or the refresh of the shadows."""
         lib, st = L.lib(), self.state.data_ptr()
         L.check(lib.rd_grad_guard(C.byref(self.desc), stream), 'rd_grad_guard')
-        L.check(lib.rd_adam_step_guarded(C.byref(self.ts.ad), st, stream), 'rd_adam_step_guarded')
+        if self.ts._optim is not None:                              # TrainStep.enable_optim: the grouped Adam under the same state word
+            self.ts._optim.enqueue(stream, st)
+        else:
+            L.check(lib.rd_adam_step_guarded(C.byref(self.ts.ad), st, stream), 'rd_adam_step_guarded')
         self.ts.wpack.refresh(stream)
         L.check(lib.rd_guard_sync(self.arr, self.table_dev.data_ptr(), self.n, self.chunks, st, stream), 'rd_guard_sync')
 

@@ -136,6 +136,7 @@ class TrainStep:
         self._slot1_keep = []
         self._after_step = None
         self._guard = None
+        self._optim = None
         self._ops = self._build_ops()
 
     def _build_ops(self):
@@ -403,6 +404,8 @@ class TrainStep:
         """Capture one step (zeroing + every launch) into a hipGraph on a side stream."""
         if self._guard is not None:
             raise RuntimeError('capture() records the classical step: the guarded tail (enable_grad_guard) is not part of a launch list')
+        if self._optim is not None:
+            raise RuntimeError('capture() records the classical step: the grouped Adam (enable_optim) is not part of a launch list')
         self._refuse_budgets_on_one_chain('capture()')
         self.wpack.refresh(self._stream())
         torch.cuda.synchronize()
@@ -454,9 +457,14 @@ class TrainStep:
             return
         if self._guard is not None:
             # the guarded tail is not in the op table of the launch list: the native call ends at the encoder backward with every
-            # lane joined, and Adam + repack follow as direct calls on the main stream (ramdsir/guard.py)
+            # lane joined, and Adam + repack follow as direct calls on the main stream (ramdsir/guard.py; with enable_optim its
+            # Adam is rd_optim_step under the guard's state word)
             self.launch(self.head_names() + self.backward_names(), join=True)
             self._guard.enqueue_tail(torch.cuda.current_stream().cuda_stream)
+        elif self._optim is not None:
+            # the grouped Adam is not in the op table either: the same cut, then rd_optim_step and the repack (ramdsir/optim.py)
+            self.launch(self.head_names() + self.backward_names(), join=True)
+            self.enqueue_optim_tail(torch.cuda.current_stream().cuda_stream)
         else:
             self.launch(self.head_names() + self.backward_names() + ('seg_c',), join_before_last=True)
         self.run_after_step()
@@ -468,6 +476,19 @@ class TrainStep:
         if self.graph is not None:
             raise RuntimeError('a captured hipGraph replays a fixed launch list: the guarded tail cannot replace its Adam')
         self._guard = guard
+
+    def enable_optim(self, optim):
+        """From now on step() runs optim.enqueue (rd_optim_step: the grouped Adam of ramdsir/optim.py) and the weight repack as direct
+        calls in place of seg_c -- under the guard's state word where enable_grad_guard is on as well.  The launch list's op table
+        and seg_c stay as they are.  A captured hipGraph replays a fixed launch list: refused."""
+        if self.graph is not None:
+            raise RuntimeError('a captured hipGraph replays a fixed launch list: the grouped Adam cannot replace its Adam')
+        self._optim = optim
+
+    def enqueue_optim_tail(self, stream):
+        """The unguarded tail with enable_optim: the grouped Adam, then the weight repack, on `stream` (a raw stream handle)."""
+        self._optim.enqueue(stream, None)
+        self.wpack.refresh(stream)
 
     def loss_dict(self):
         """Synchronises.  Names follow the tensorboard scalars of train.py:298-304."""

@@ -29,6 +29,7 @@ class FusedTrainer:
         self.ts.wpack.refresh()
         self._primed, self._graphs, self._announced = False, bool(use_graph), None
         self._tb, self._tb_pending, self._tb_hook, self._log, self._avg, self._guard = None, None, None, None, None, None
+        self._optim = None
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -132,6 +133,21 @@ class FusedTrainer:
         self._guard = guard.GradGuard(self, max_norm)
         self.ts.enable_grad_guard(self._guard)
         return self._guard
+
+    def enable_optim(self, weight_decay=0.0, wd_mode='decoupled', lr_schedule='poly', warmup_iters=0, enc_lr_mult=0.5):
+        """From now on every step() runs the grouped Adam (ramdsir/optim.py, rd_optim_step) in place of rd_adam_step: the arena as a
+        device table of ranges, each with its learning-rate multiplier (enc_lr_mult inside the encoder, 1 elsewhere) and its weight
+        decay (weight_decay on tensors with more than one dimension -- the conv kernels; biases and BatchNorm weight / bias are
+        exempt), decoupled (AdamW) or L2 (Adam(weight_decay)); the schedule (poly with the reference's lag, cosine, constant) and a
+        linear warm-up are evaluated on the device from the counter.  The default values give the reference's optimizer, bit for
+        bit.  Counter, schedule words and lr() are rd_adam_step's; with enable_grad_guard (in either order) the guard's tail calls it
+        under its state word.  Returns the optim.GroupedAdam.  Not with use_graph=True."""
+        if self._graphs:
+            raise RuntimeError('enable_optim: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        from . import optim
+        self._optim = optim.GroupedAdam(self, weight_decay, wd_mode, lr_schedule, warmup_iters, enc_lr_mult)
+        self.ts.enable_optim(self._optim)
+        return self._optim
 
     def enable_step_log(self, health=False, rows=256):
         """From now on every step() appends one row to a device-resident ring (ramdsir/step_log.py, rd_step_log): the losses, the lr and

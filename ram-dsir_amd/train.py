@@ -23,7 +23,9 @@ one where --fused_val is in use (<target>_val_log_avg.csv, model_avg_%.2f.pth) a
 last iterate only; (vii) --clip_grad_norm X clips the gradient of the whole model by its global norm in front of Adam and
 --skip_nonfinite makes a step with a non-finite gradient leave no trace in the model state (parameters, moments, BatchNorm buffers),
 both decided on the device (ramdsir/guard.py: rd_grad_guard, rd_adam_step_guarded, rd_guard_sync); the reference steps on whatever
-gradient it gets (code/train.py:285-287).
+gradient it gets (code/train.py:285-287); (viii) --weight_decay / --wd_mode / --lr_schedule / --warmup_iters / --enc_lr_mult replace the
+reference's one hard-coded optimizer line (Adam without decay, lr / 2 on the encoder, poly; code/train.py:573-576, 289-293) by a grouped
+Adam whose ranges, decay and schedule live on the device (ramdsir/optim.py, rd_optim_step); their defaults ARE that line.
 """
 import argparse
 import os
@@ -150,6 +152,23 @@ def parse_args(argv=None):
                    help='a step whose gradient holds a NaN or an infinity, or whose norm is not finite, leaves no trace in the model: '
                         'parameters and Adam moments stay, every BatchNorm buffer is rolled back, the bias corrections count the updates '
                         'applied; the iteration counter (and with it the lr schedule) still advances; --norm bn only; off by default')
+    p.add_argument('--weight_decay', type=float, default=0.0, metavar='W',
+                   help='weight decay of the fused step\'s Adam (ramdsir/optim.py, rd_optim_step), applied to tensors with more than one '
+                        'dimension -- the convolution kernels; 1-D tensors (biases, BatchNorm weight and bias) are exempt; W >= 0 and '
+                        'finite; --norm bn only; default 0')
+    p.add_argument('--wd_mode', choices=['decoupled', 'l2'], default='decoupled',
+                   help='--weight_decay: decoupled multiplies the parameter by 1 - lr * W in front of the update (torch.optim.AdamW, with '
+                        'the lr of the parameter\'s group); l2 adds W * parameter to the gradient (torch.optim.Adam(weight_decay), behind '
+                        '--clip_grad_norm\'s scale); l2 needs --weight_decay; default decoupled')
+    p.add_argument('--lr_schedule', choices=['poly', 'cosine', 'constant'], default='poly',
+                   help='poly: the reference\'s lr * (1 - iter / total) ^ 0.9, one iteration behind as there (code/train.py:289-293); cosine: '
+                        '0.5 * lr * (1 + cos(pi * iter / total)); constant: lr; evaluated on the device; --norm bn only; default poly')
+    p.add_argument('--warmup_iters', type=int, default=0, metavar='N',
+                   help='multiply the scheduled lr of iteration i by min(1, (i + 1) / N); fewer than the run\'s iterations; --norm bn '
+                        'only; default 0 (none)')
+    p.add_argument('--enc_lr_mult', type=float, default=0.5, metavar='M',
+                   help='the encoder\'s learning rate as a multiple of --lr; M > 0 and finite; --norm bn only; default 0.5, the '
+                        'reference\'s lr / 2 (code/train.py:573)')
     return p.parse_args(argv)
 
 
@@ -473,6 +492,20 @@ def guard_suffix(g):
     return ' grad_norm %.4g scale %.4g clipped %d skipped %d' % (g['norm'], g['scale'], g['clipped'], g['skipped'])
 
 
+OPTIM_DEFAULTS = dict(weight_decay=0.0, wd_mode='decoupled', lr_schedule='poly', warmup_iters=0, enc_lr_mult=0.5)
+
+
+def optim_settings(args):
+    """The five optimizer flags as FusedTrainer.enable_optim takes them."""
+    return {k: getattr(args, k) for k in OPTIM_DEFAULTS}
+
+
+def uses_optim(args):
+    """Any of the five flags away from its default turns the grouped Adam on (ramdsir/optim.py); with all five at their defaults
+    nothing is constructed and the step is the reference's rd_adam_step, launch for launch."""
+    return any(getattr(args, k) != v for k, v in OPTIM_DEFAULTS.items())
+
+
 def val_log_path(args, suffix=''):
     return osp.join(args.save_path, str(args.test_domain_idx) + '_val_log%s.csv' % suffix)
 
@@ -549,6 +582,18 @@ def check_args(args, world):
     if uses_guard(args) and args.norm != 'bn':
         raise ValueError('--clip_grad_norm / --skip_nonfinite guard the fused step\'s Adam launch: --norm %s trains through the modules, '
                          'whose Adam is torch\'s' % args.norm)
+    # (the kernel receives both factors as float32: values that are infinite there are refused with the ones infinite as given)
+    if not 0.0 <= args.weight_decay <= float(np.finfo(np.float32).max):                                           # NaN fails both
+        raise ValueError('--weight_decay takes a decay that is 0 or positive and finite, got %r' % args.weight_decay)
+    if args.wd_mode != 'decoupled' and not args.weight_decay > 0:
+        raise ValueError('--wd_mode shapes the weight decay: it needs --weight_decay')
+    if args.warmup_iters < 0:
+        raise ValueError('--warmup_iters takes a number of iterations, got %d' % args.warmup_iters)
+    if not 0.0 < args.enc_lr_mult <= float(np.finfo(np.float32).max) or float(np.float32(args.enc_lr_mult)) == 0.0:
+        raise ValueError('--enc_lr_mult takes a positive finite multiplier, got %r' % args.enc_lr_mult)
+    if uses_optim(args) and args.norm != 'bn':
+        raise ValueError('--weight_decay / --wd_mode / --lr_schedule / --warmup_iters / --enc_lr_mult shape the fused step\'s Adam launch: '
+                         '--norm %s trains through the modules, whose Adam is torch\'s' % args.norm)
 
 
 class TrainLog:
@@ -673,6 +718,23 @@ def build_trainer(args, rank, raw, resident, batch_sizes, max_len):
     return (encoder, seg_decoder, rec_decoder), trainer, (H, W), total_iters
 
 
+def check_warmup(args, total_iters):
+    """The one refusal that needs the length of the run: where total_iters becomes known, in front of any optimizer launch."""
+    if args.warmup_iters >= total_iters:
+        raise ValueError('--warmup_iters %d is not below the %d iterations of this run' % (args.warmup_iters, total_iters))
+
+
+def enable_optim(args, trainer, total_iters, rank=0):
+    """The grouped Adam of the five optimizer flags on the trainer, with its one summary line."""
+    check_warmup(args, total_iters)
+    optim = trainer.enable_optim(**optim_settings(args))
+    if rank == 0:
+        print('optim: %s schedule, warmup %d, encoder lr x %g; weight decay %g (%s) over %d ranges, %d of %d elements decay'
+              % (args.lr_schedule, args.warmup_iters, args.enc_lr_mult, args.weight_decay, args.wd_mode, optim.n,
+                 optim.decayed_elements(), trainer.bank.n))
+    return optim
+
+
 def restore_host_side(args, meta, loaders, raw):
     """The host side of a --resume snapshot, behind every start-up draw (the validation start, the loaders' construction,
     next(iter(raw[0]))): the three generators and the cycles (replaced in `loaders`) as the snapshotted process left them at the end
@@ -731,16 +793,19 @@ def init_process(world, local):
     return dist.new_group(backend='gloo') if world > 1 else None
 
 
-def open_state(args, trainer, fingerprint_args, resume_state, avg=None, guard=None):
+def open_state(args, trainer, fingerprint_args, resume_state, avg=None, guard=None, optim=None):
     """--ckpt_every / --resume, device side: the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py);
     --resume: the arenas, the BatchNorm buffers and the schedule counter from the file (restore_host_side follows before the loop).
     avg (--avg_weights): the averaged model's ranges go behind the trainer's; a file and a run that disagree about them are refused.
     guard (--clip_grad_norm / --skip_nonfinite): its state word goes behind those, under the same rule; behind a restore its shadow
-    copies are taken from the restored BatchNorm buffers."""
+    copies are taken from the restored BatchNorm buffers.  optim (the five optimizer flags): no range of its own -- its state is the
+    arenas, the counter and the schedule words; a file taken under other settings (or, without the record, under the defaults) is
+    refused."""
     from ramdsir import ckpt
     if resume_state is not None:
         ckpt.compare_avg_weights(resume_state, avg.settings() if avg is not None else None)
         ckpt.compare_grad_guard(resume_state, guard.settings() if guard is not None else None)
+        ckpt.compare_optim(resume_state, optim.settings() if optim is not None else None)
     extra = (avg.named_ranges() if avg is not None else []) + (guard.named_ranges() if guard is not None else [])
     state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, *fingerprint_args), extra=extra or None)
     if resume_state is not None:
@@ -817,7 +882,9 @@ def main(args):
     avg = trainer.enable_avg_weights(*avg_settings(args)) if uses_avg(args) else None
     # --clip_grad_norm / --skip_nonfinite: the guarded tail replaces Adam + repack in the step; the shadows copy the initial buffers
     guard = trainer.enable_grad_guard(guard_max_norm(args)) if uses_guard(args) else None
-    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg, guard) if uses_ckpt(args) else None
+    # the five optimizer flags: the grouped Adam replaces rd_adam_step in the step (under the guard's state word where both are on)
+    optim = enable_optim(args, trainer, total_iters, rank) if uses_optim(args) else None
+    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg, guard, optim) if uses_ckpt(args) else None
     if val is not None:
         val.bind(trainer)
         if avg is not None and val.mode != 'fused':
@@ -872,6 +939,8 @@ def main(args):
                                            val_log_bytes=os.path.getsize(avg_log) if os.path.exists(avg_log) else 0)
             if guard is not None:
                 meta['grad_guard'] = guard.settings()
+            if optim is not None:
+                meta['optim'] = optim.settings()
             state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), meta)
         if rank == 0:
             t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * log.imgs_per_iter
