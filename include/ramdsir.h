@@ -974,6 +974,35 @@ typedef struct {
 int rd_optim_step(const rd_optim_t* p, const rd_optim_range_t* table_host, const rd_optim_range_t* table_dev, int n_ranges,
                   int64_t total_chunks, const rd_guard_state_t* guard_dev /* may be NULL */, void* stream);
 
+/* Gradient accumulation (train.py --accum_steps N, ramdsir/accum.py), csrc/accum.hip: the optimizer tail of the fused step runs on
+ * every N-th iteration only, on the MEAN of the N micro-batch gradients.  The writers of the gradient arena overwrite (and rd_zero at
+ * the head of every step is part of the contract of the ones that add), so the running sum lives in a second fp32 arena `acc` of the
+ * same length and ONE launch per iteration stands between the encoder backward and the tail.  No reference counterpart: the
+ * reference's batch sizes are its tables (code/train.py:35-45).
+ *
+ * grad = the step's gradient arena, n elements; k = the position of this micro-batch in its window of `steps`; per element, every
+ * operation a separately rounded fp32 operation (never an fma):
+ *     steps == 1:          returns 0, launches nothing
+ *     k == 0:              acc = grad                          a word copy -- the bits, NaN payloads included; grad is not written
+ *     0 < k < steps - 1:   acc = acc + grad                    grad is not written
+ *     k == steps - 1:      grad = (acc + grad) * inv_steps     in place in the gradient arena; acc is not written
+ * so rd_adam_step, rd_grad_guard + rd_adam_step_guarded and rd_optim_step read the arena they always read.  inv_steps is
+ * (float)(1.0 / steps), formed once by the caller; another bit pattern is refused.  ramdsir/accum.py model() is the same arithmetic
+ * in numpy.  (The payload of a NaN that an addition PRODUCES -- inf + -inf -- is the hardware's; every other bit is the model's.)
+ *
+ * Elementwise: no LDS, no atomics, no reduction.  One range, so rd_adam_step's grid-stride form (at most 1024 workgroups of 256
+ * threads).  Where grad and acc share a 16-byte phase the part behind the first 16-byte boundary moves with 16-byte accesses and
+ * the (at most six) words in front of and behind it one by one; arenas of different phase go word by word throughout.  Every load
+ * of a thread's batch is issued before its first store.
+ *
+ * Returns, before anything is launched: -1 a null grad or acc; -2 a pointer that is not 4-byte aligned; -3 n < 1 (or above
+ * RD_ACCUM_MAX_N); -4 steps outside 1..RD_ACCUM_MAX_STEPS; -5 k outside [0, steps); -6 an inv_steps whose bits are not those of
+ * (float)(1.0 / steps); -7 [grad, grad + n) and [acc, acc + n) overlap.  Nothing is allocated, synchronised or copied; the launch goes
+ * through the library's one launch site. */
+#define RD_ACCUM_MAX_STEPS 65536
+#define RD_ACCUM_MAX_N (1ll << 40)
+int rd_grad_accum(float* grad, float* acc, int64_t n, int32_t k, int32_t steps, float inv_steps, void* stream);
+
 /* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
  * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
  * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */

@@ -203,6 +203,9 @@ class RdOptimRange(C.Structure):
     _fields_ = [('first', i64), ('count', i64), ('lr_mult', f32), ('weight_decay', f32), ('chunk0', i64)]
 
 
+ACCUM_MAX_STEPS = 65536                                             # RD_ACCUM_MAX_STEPS
+
+
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
     _fields_ = [('op', i32), ('lane', i32), ('wait_main', i32), ('nargs', i32), ('a', C.c_uint64 * 18)]
@@ -293,6 +296,7 @@ _SIGS = {
     'rd_adam_step_guarded': (C.c_int, [C.POINTER(RdAdam), vp, vp]),
     'rd_guard_sync': (C.c_int, [C.POINTER(RdGuardRange), vp, C.c_int, i64, vp, vp]),
     'rd_optim_step': (C.c_int, [C.POINTER(RdOptim), C.POINTER(RdOptimRange), vp, C.c_int, i64, vp, vp]),
+    'rd_grad_accum': (C.c_int, [fp, fp, i64, i32, i32, f32, vp]),
     'rd_crc32c':(C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),

@@ -13,7 +13,9 @@ averaged model ('avg/...', ramdsir/avg.py) follow the trainer's and its settings
 with --clip_grad_norm / --skip_nonfinite the guard's state word ('guard/state', ramdsir/guard.py) follows those and its max_norm sits
 under meta['grad_guard'] (compare_grad_guard); the settings of the grouped Adam (--weight_decay, --wd_mode, --lr_schedule,
 --warmup_iters, --enc_lr_mult; ramdsir/optim.py) sit under meta['optim'] (compare_optim) -- it adds no range: its state is the
-arenas, the counter and the schedule words.
+arenas, the counter and the schedule words; with --accum_steps N > 1 the accumulator arena ('accum/arena', ramdsir/accum.py) goes behind
+the other extra ranges (with the guard on, its shadow copies of the BatchNorm buffers too: in mid-window they differ from the live
+ones) and N and the position in the window sit under meta['grad_accum'] (compare_grad_accum).
 
 Checksums of the little-endian uint32 words w[0 .. m) of a range: s1 = sum w[i], s2 = sum (i + 1) w[i], both mod 2^64 (`checksums`
 is the numpy model the kernel equals bit for bit; s2 depends on the order of the words, s1 does not).
@@ -189,6 +191,30 @@ def compare_optim(state, current):
     for k in OPTIM_DEFAULTS:
         if saved[k] != now[k]:
             raise ValueError('--resume: the snapshot was taken with optim %s = %r, this run has %r' % (k, saved[k], now[k]))
+
+
+ACCUM_PREFIX = 'accum/'         # the accumulator arena of --accum_steps (ramdsir/accum.py named_ranges)
+
+
+def compare_grad_accum(state, current):
+    """--resume with / without --accum_steps.  current: the run's settings (accum.GradAccum.settings()) or None when N is 1.  The
+    record travels under meta['grad_accum'] = dict(steps=N, micro=k) -- k the position in the window the snapshot was taken at, which
+    the restore hands to GradAccum.set_position; a file without the record was taken with N = 1 and resumes only so.  ValueError
+    naming grad_accum where file and run differ in N (the counter, the schedule and a half-filled arena all mean something else under
+    another N), or where the record and the file's ranges contradict one another.  Returns the position to continue at."""
+    saved = (state.get('meta') or {}).get('grad_accum')
+    has = any(e['name'].startswith(ACCUM_PREFIX) for e in state['table'])
+    was = int(saved['steps']) if saved else 1
+    now = int(current['steps']) if current else 1
+    if was != now:
+        raise ValueError('--resume: the snapshot was taken with grad_accum steps = %d, this run has %d' % (was, now))
+    if has != (was > 1):
+        raise ValueError('--resume: the snapshot records grad_accum steps = %d but %s' % (was, 'holds an accumulator arena' if has else
+                                                                                          'holds no accumulator arena'))
+    micro = int(saved.get('micro', 0)) if saved else 0
+    if not 0 <= micro < was:
+        raise ValueError('--resume: the snapshot records grad_accum micro = %d in a window of %d' % (micro, was))
+    return micro
 
 
 # ------------------------------------------------------------------------------------------------------------- the file

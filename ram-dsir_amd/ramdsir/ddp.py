@@ -198,6 +198,8 @@ class DataParallelStep:
     def step(self):
         main = torch.cuda.current_stream()
         works = []
+        if self.ts._accum is not None:
+            raise RuntimeError('gradient accumulation (enable_grad_accum) runs in one process: the data-parallel step would apply every micro-batch')
         if self.graphs is not None and (self.ts._slot != 0 or self.ts._x_ready or self.ts._next_loaded):
             raise RuntimeError('captured graphs replay the classical step on input slot 0: do not mix them with load_raw_next()')
         if self.graphs is not None and self.ts._after_step is not None:

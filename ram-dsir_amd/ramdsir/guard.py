@@ -223,3 +223,8 @@ class GradGuard:
         """[(name, tensor)] for ckpt.TrainState's extra ranges: the state word, whose `skipped` count Adam's bias corrections depend on.
         The shadows are not state: behind a completed step they equal the live buffers (sync_shadow() after a restore)."""
         return [('guard/state', self.state)]
+
+    def shadow_ranges(self):
+        """[(name, tensor)] of the shadow copies, 'guard/shadow/<module>/<key>': state only under gradient accumulation
+        (ramdsir/accum.py), where a snapshot in mid-window finds them at the window's start while the live buffers have moved."""
+        return [(name, shadow) for name, _, shadow in self.ranges]

@@ -137,6 +137,7 @@ class TrainStep:
         self._after_step = None
         self._guard = None
         self._optim = None
+        self._accum = None
         self._ops = self._build_ops()
 
     def _build_ops(self):
@@ -406,6 +407,8 @@ class TrainStep:
             raise RuntimeError('capture() records the classical step: the guarded tail (enable_grad_guard) is not part of a launch list')
         if self._optim is not None:
             raise RuntimeError('capture() records the classical step: the grouped Adam (enable_optim) is not part of a launch list')
+        if self._accum is not None:
+            raise RuntimeError('capture() records the classical step: gradient accumulation (enable_grad_accum) is not part of a launch list')
         self._refuse_budgets_on_one_chain('capture()')
         self.wpack.refresh(self._stream())
         torch.cuda.synchronize()
@@ -455,7 +458,20 @@ class TrainStep:
                 raise RuntimeError('a captured hipGraph replays a fixed launch list: nothing can be armed behind its step')
             self.graph.replay()
             return
-        if self._guard is not None:
+        if self._accum is not None:
+            # gradient accumulation (ramdsir/accum.py) takes the same cut: the native call ends at the encoder backward with every
+            # lane joined, rd_grad_accum follows, and only the window's last micro-batch is followed by the tail that applies
+            self.launch(self.head_names() + self.backward_names(), join=True)
+            stream = torch.cuda.current_stream().cuda_stream
+            if self._accum.enqueue(stream):
+                if self._guard is not None:
+                    self._guard.enqueue_tail(stream)
+                elif self._optim is not None:
+                    self.enqueue_optim_tail(stream)
+                else:
+                    L.check(L.lib().rd_adam_step(C.byref(self.ad), stream), 'rd_adam_step')
+                    self.wpack.refresh(stream)
+        elif self._guard is not None:
             # the guarded tail is not in the op table of the launch list: the native call ends at the encoder backward with every
             # lane joined, and Adam + repack follow as direct calls on the main stream (ramdsir/guard.py; with enable_optim its
             # Adam is rd_optim_step under the guard's state word)
@@ -484,6 +500,16 @@ class TrainStep:
         if self.graph is not None:
             raise RuntimeError('a captured hipGraph replays a fixed launch list: the grouped Adam cannot replace its Adam')
         self._optim = optim
+
+    def enable_grad_accum(self, accum):
+        """From now on step() ends its native call at the encoder backward, runs accum.enqueue (rd_grad_accum, ramdsir/accum.py) and
+        only at the last micro-batch of a window the tail that applies: guard.enqueue_tail where enable_grad_guard is on,
+        enqueue_optim_tail where enable_optim is on, otherwise rd_adam_step and the weight repack as direct calls.  The launch list's
+        op table and seg_c stay as they are; the per-step rd_zero, the pipelined RAM of the next batch and the input slots are
+        untouched.  A captured hipGraph replays a fixed launch list: refused."""
+        if self.graph is not None:
+            raise RuntimeError('a captured hipGraph replays a fixed launch list: gradient accumulation cannot cut its step')
+        self._accum = accum
 
     def enqueue_optim_tail(self, stream):
         """The unguarded tail with enable_optim: the grouped Adam, then the weight repack, on `stream` (a raw stream handle)."""

@@ -30,6 +30,7 @@ class FusedTrainer:
         self._primed, self._graphs, self._announced = False, bool(use_graph), None
         self._tb, self._tb_pending, self._tb_hook, self._log, self._avg, self._guard = None, None, None, None, None, None
         self._optim = None
+        self._accum = None
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -95,6 +96,8 @@ class FusedTrainer:
         the host last.  All three only read the step's buffers, so the order changes no result.  Nothing is armed when none applies."""
         tb, self._tb_hook = self._tb_hook, None
         log, avg = self._log, self._avg
+        if avg is not None and self._accum is not None and not self._accum.next_is_boundary():
+            avg = None                                      # rd_avg_step reads the counter, which moves at a window's last step only
         if tb is None and log is None and avg is None:
             return
 
@@ -148,6 +151,29 @@ class FusedTrainer:
         self._optim = optim.GroupedAdam(self, weight_decay, wd_mode, lr_schedule, warmup_iters, enc_lr_mult)
         self.ts.enable_optim(self._optim)
         return self._optim
+
+    def enable_grad_accum(self, steps):
+        """From now on every step() runs forward, losses and backward as ever and is followed by one rd_grad_accum launch
+        (ramdsir/accum.py); the optimizer tail -- rd_adam_step + repack, the guarded tail or the grouped Adam, whichever is enabled,
+        in either order with this call -- runs behind every `steps`-th step only, on the mean of the window's gradients.  The device
+        iteration counter, the schedule (`total_iters` is a number of UPDATES), the bias corrections and the start of
+        enable_avg_weights count updates; the weight average moves at a window's last step only; BatchNorm moves its running
+        statistics at every step, and a window the guard skips rolls them back over all of its forward passes.  losses() and lr()
+        report the current micro-batch's losses and the last update's rate.  steps == 1 constructs nothing and returns None.  Not
+        with use_graph=True, not data parallel."""
+        from . import accum
+        steps = accum.check_steps(steps)
+        if self._graphs:
+            raise RuntimeError('enable_grad_accum: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        if self.world > 1:
+            raise RuntimeError('enable_grad_accum: gradient accumulation runs in one process (the bucketed gradient exchange of %d ranks '
+                               'is tied to the segments of the step)' % self.world)
+        if steps == 1:
+            return None
+        acc = accum.GradAccum(self, steps)
+        self.ts.enable_grad_accum(acc)                      # (refuses a captured step: nothing is left half-enabled)
+        self._accum = acc
+        return acc
 
     def enable_step_log(self, health=False, rows=256):
         """From now on every step() appends one row to a device-resident ring (ramdsir/step_log.py, rd_step_log): the losses, the lr and

@@ -25,7 +25,10 @@ last iterate only; (vii) --clip_grad_norm X clips the gradient of the whole mode
 both decided on the device (ramdsir/guard.py: rd_grad_guard, rd_adam_step_guarded, rd_guard_sync); the reference steps on whatever
 gradient it gets (code/train.py:285-287); (viii) --weight_decay / --wd_mode / --lr_schedule / --warmup_iters / --enc_lr_mult replace the
 reference's one hard-coded optimizer line (Adam without decay, lr / 2 on the encoder, poly; code/train.py:573-576, 289-293) by a grouped
-Adam whose ranges, decay and schedule live on the device (ramdsir/optim.py, rd_optim_step); their defaults ARE that line.
+Adam whose ranges, decay and schedule live on the device (ramdsir/optim.py, rd_optim_step); their defaults ARE that line; (ix)
+--accum_steps N applies the optimizer at every N-th iteration, on the mean of the N micro-batch gradients (ramdsir/accum.py,
+rd_grad_accum: one HIP launch per iteration into a second gradient arena) -- the effective batch is N times the reference's per-domain
+tables (code/train.py:35-45), which stay as they are; the schedule counts updates, the loop counts iterations.
 """
 import argparse
 import os
@@ -169,6 +172,15 @@ def parse_args(argv=None):
     p.add_argument('--enc_lr_mult', type=float, default=0.5, metavar='M',
                    help='the encoder\'s learning rate as a multiple of --lr; M > 0 and finite; --norm bn only; default 0.5, the '
                         'reference\'s lr / 2 (code/train.py:573)')
+    p.add_argument('--accum_steps', type=int, default=1, metavar='N',
+                   help='gradient accumulation: forward, losses and backward run at every iteration as ever, the optimizer (with '
+                        '--clip_grad_norm / --skip_nonfinite, the optimizer flags and --avg_weights where they are on) at every N-th '
+                        'iteration only, on the mean of the N micro-batch gradients, summed in a second arena by one HIP launch per '
+                        'iteration (ramdsir/accum.py, rd_grad_accum); the lr schedule, --warmup_iters and --avg_start count updates '
+                        '(iterations // N), epochs, --max_iters and --tb_images count iterations, trailing iterations that complete no '
+                        'window are never applied; BatchNorm moves its running statistics at every iteration; the --log_every console and '
+                        'scalar lines and --tb_images report the current micro-batch\'s losses and the last update\'s lr, not window '
+                        'means; --norm bn, one process, not with --tb_every_iter / --tb_health; default 1 (off)')
     return p.parse_args(argv)
 
 
@@ -506,6 +518,28 @@ def uses_optim(args):
     return any(getattr(args, k) != v for k, v in OPTIM_DEFAULTS.items())
 
 
+def uses_accum(args):
+    """--accum_steps above 1 turns gradient accumulation on (ramdsir/accum.py); at 1 nothing is constructed and the step is the
+    unflagged one, launch for launch."""
+    return args.accum_steps != 1
+
+
+def accum_totals(args, max_len):
+    """(updates, iterations, trailing iterations that complete no window) of the run: the schedule, --warmup_iters and the fingerprint
+    count updates, the loop counts iterations.  A run with no complete window is refused."""
+    iterations = max_len * args.epochs
+    updates, trailing = iterations // args.accum_steps, iterations % args.accum_steps
+    if updates < 1 and uses_accum(args):
+        raise ValueError('--accum_steps %d: the %d iterations of this run complete no window (no optimizer update would be applied)'
+                         % (args.accum_steps, iterations))
+    return updates, iterations, trailing
+
+
+def accum_line(steps, updates, iterations, trailing):
+    return ('accum: %d micro-batches per update: %d updates over %d iterations, %d trailing iteration%s applied'
+            % (steps, updates, iterations, trailing, ' is not' if trailing == 1 else 's are not'))
+
+
 def val_log_path(args, suffix=''):
     return osp.join(args.save_path, str(args.test_domain_idx) + '_val_log%s.csv' % suffix)
 
@@ -594,6 +628,19 @@ def check_args(args, world):
     if uses_optim(args) and args.norm != 'bn':
         raise ValueError('--weight_decay / --wd_mode / --lr_schedule / --warmup_iters / --enc_lr_mult shape the fused step\'s Adam launch: '
                          '--norm %s trains through the modules, whose Adam is torch\'s' % args.norm)
+    if args.accum_steps < 1:
+        raise ValueError('--accum_steps takes a number of micro-batches per update, got %d' % args.accum_steps)
+    if args.accum_steps > 65536:
+        raise ValueError('--accum_steps takes at most 65536 micro-batches per update, got %d' % args.accum_steps)
+    if uses_accum(args) and args.norm != 'bn':
+        raise ValueError('--accum_steps accumulates the fused step\'s gradient arena in front of its Adam launch: --norm %s trains through '
+                         'the modules, whose Adam is torch\'s' % args.norm)
+    if uses_accum(args) and world > 1:
+        raise ValueError('--accum_steps runs in one process: the bucketed gradient exchange is tied to the segments of the step '
+                         '(WORLD_SIZE=%d)' % world)
+    if uses_accum(args) and uses_step_log(args):
+        raise ValueError('--accum_steps does not go with --tb_every_iter / --tb_health: the rows of the per-step ring are keyed by the '
+                         'optimizer\'s counter, which moves once per window')
 
 
 class TrainLog:
@@ -704,7 +751,8 @@ def build_trainer(args, rank, raw, resident, batch_sizes, max_len):
     from ramdsir.trainer import FusedTrainer, ModuleTrainer
     sample = next(iter(raw[0]))
     H, W = resident.hw if resident is not None else sample[0].shape[1:3]
-    total_iters = max_len * args.epochs
+    # what the trainer's schedule, the warm-up check and the fingerprint count: optimizer updates (--accum_steps: iterations // N)
+    total_iters = accum_totals(args, max_len)[0]
     cons = args.consistency_type if args.consistency else None
     assert cons in (None, 'mse', 'kd'), args.consistency_type
     # --norm bn (the reference's default): the fused HIP step.  gn / in: the reference's own loop over the drop-in modules (the fused step
@@ -793,24 +841,33 @@ def init_process(world, local):
     return dist.new_group(backend='gloo') if world > 1 else None
 
 
-def open_state(args, trainer, fingerprint_args, resume_state, avg=None, guard=None, optim=None):
+def open_state(args, trainer, fingerprint_args, resume_state, avg=None, guard=None, optim=None, accum=None):
     """--ckpt_every / --resume, device side: the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py);
     --resume: the arenas, the BatchNorm buffers and the schedule counter from the file (restore_host_side follows before the loop).
     avg (--avg_weights): the averaged model's ranges go behind the trainer's; a file and a run that disagree about them are refused.
     guard (--clip_grad_norm / --skip_nonfinite): its state word goes behind those, under the same rule; behind a restore its shadow
     copies are taken from the restored BatchNorm buffers.  optim (the five optimizer flags): no range of its own -- its state is the
     arenas, the counter and the schedule words; a file taken under other settings (or, without the record, under the defaults) is
-    refused."""
+    refused.  accum (--accum_steps N > 1): the accumulator arena goes behind the other extra ranges -- a window that straddles an
+    epoch boundary is open when the snapshot is taken -- and, with the guard on, so do the guard's shadow copies, which in mid-window
+    hold the BatchNorm buffers of the window's START; a file taken under another N (without the record: N = 1) is refused; the restore
+    sets the host-side position in the window."""
     from ramdsir import ckpt
+    micro = 0
     if resume_state is not None:
         ckpt.compare_avg_weights(resume_state, avg.settings() if avg is not None else None)
         ckpt.compare_grad_guard(resume_state, guard.settings() if guard is not None else None)
         ckpt.compare_optim(resume_state, optim.settings() if optim is not None else None)
+        micro = ckpt.compare_grad_accum(resume_state, accum.settings() if accum is not None else None)
     extra = (avg.named_ranges() if avg is not None else []) + (guard.named_ranges() if guard is not None else [])
+    if accum is not None:
+        extra += (guard.shadow_ranges() if guard is not None else []) + accum.named_ranges()
     state_io = ckpt.TrainState(trainer, ckpt.fingerprint(args, trainer, *fingerprint_args), extra=extra or None)
     if resume_state is not None:
         state_io.restore(resume_state)
-        if guard is not None:
+        if accum is not None:
+            accum.set_position(micro)
+        elif guard is not None:
             guard.sync_shadow()
     if not args.gpu_data and args.num_workers > 0:
         print('ckpt: model, optimizer and schedule state are restored exactly; with DataLoader worker processes the draws come from '
@@ -866,6 +923,8 @@ def main(args):
     os.makedirs(args.save_path, exist_ok=True)
     bsl = (fundus_batch_list if args.dataset == 'fundus' else prostate_batch_list)[args.test_domain_idx][:len(domain_idx_list)]
     raw, samplers, loaders, max_len = make_loaders(args, data_root, world, rank, bsl, domain_idx_list, replay=uses_ckpt(args))
+    if uses_accum(args):
+        accum_totals(args, max_len)                                  # a run with no complete window is refused here
     resident = None
     if args.gpu_data:
         # decode once, keep the pixels on this GPU (ramdsir/gpu_data.py); the loaders above only draw
@@ -884,7 +943,12 @@ def main(args):
     guard = trainer.enable_grad_guard(guard_max_norm(args)) if uses_guard(args) else None
     # the five optimizer flags: the grouped Adam replaces rd_adam_step in the step (under the guard's state word where both are on)
     optim = enable_optim(args, trainer, total_iters, rank) if uses_optim(args) else None
-    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg, guard, optim) if uses_ckpt(args) else None
+    # --accum_steps: one rd_grad_accum launch behind every backward pass, the tail above behind every N-th (total_iters counts updates)
+    accum = trainer.enable_grad_accum(args.accum_steps) if uses_accum(args) else None
+    if accum is not None and rank == 0:
+        print(accum_line(args.accum_steps, *accum_totals(args, max_len)))
+    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg, guard, optim, accum) \
+        if uses_ckpt(args) else None
     if val is not None:
         val.bind(trainer)
         if avg is not None and val.mode != 'fused':
@@ -941,6 +1005,8 @@ def main(args):
                 meta['grad_guard'] = guard.settings()
             if optim is not None:
                 meta['optim'] = optim.settings()
+            if accum is not None:                       # an odd epoch length leaves a window open across the epoch boundary
+                meta['grad_accum'] = dict(accum.settings(), micro=accum.position())
             state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), meta)
         if rank == 0:
             t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * log.imgs_per_iter
