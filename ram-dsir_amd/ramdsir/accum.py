@@ -12,8 +12,8 @@ rd_adam_step, the guarded tail (ramdsir/guard.py) and the grouped Adam (ramdsir/
 What follows from it: the device iteration counter, the schedule, the bias corrections and --avg_start count UPDATES; BatchNorm
 normalises every micro-batch by its own statistics and moves its running statistics at every iteration (what a torch loop with
 (loss / N).backward() does); with the guard on, norm, clip and verdict are those of the mean gradient and a skipped window rolls the
-BatchNorm buffers back over all N forward passes.  The op table of the native launch list is ABI, so TrainStep.step() ends its native
-call at the encoder backward with every lane joined (the cut of the guard and of the grouped Adam) and enqueues from here.
+BatchNorm buffers back over all N forward passes.  The launch is the first call of TrainStep.enqueue_tail (ramdsir/step.py, which says
+where the native call is cut and in which order the tail runs): within an open window it is the only one.
 
     GradAccum.enqueue(stream) -> bool   one rd_grad_accum call (one launch); True at the window's last micro-batch
     GradAccum.next_is_boundary()        whether the next enqueue() completes a window
@@ -109,7 +109,7 @@ class GradAccum:
 
     def enqueue(self, stream):
         """The launch behind whatever `stream` holds (the encoder backward, every lane joined).  True at the window's last micro-batch:
-        the gradient arena then holds the mean and the caller enqueues the tail."""
+        the gradient arena then holds the mean and the caller (TrainStep.enqueue_tail) goes on with the tail."""
         k = self.micro
         L.check(L.lib().rd_grad_accum(self.bank.grads.data_ptr(), self.acc.data_ptr(), self.bank.n, k, self.steps, float(self.inv), stream),
                 'rd_grad_accum')

@@ -138,47 +138,39 @@ def compare_fingerprints(saved, current):
 
 AVG_PREFIX = 'avg/'             # the ranges of the averaged model (ramdsir/avg.py named_ranges)
 AVG_SETTINGS = ('mode', 'decay', 'start')
-
-
-def compare_avg_weights(state, current):
-    """--resume with / without --avg_weights.  current: the run's settings (avg.WeightAverage.settings()) or None when the flag is off.
-    ValueError naming avg_weights where the file has no averaged ranges and the run wants them, has them and the run does not, or was
-    taken under other settings: an average cannot be made up, dropped or continued under another rule in the middle of a run."""
-    saved = (state.get('meta') or {}).get('avg_weights')
-    has = any(e['name'].startswith(AVG_PREFIX) for e in state['table'])
-    if current is not None and not (has and saved):
-        raise ValueError('--resume: the snapshot holds no averaged model (it was taken without --avg_weights); this run has avg_weights = %r'
-                         % (dict(current),))
-    if current is None and (has or saved):
-        raise ValueError('--resume: the snapshot holds an averaged model (avg_weights = %r); this run was started without --avg_weights'
-                         % ({k: saved.get(k) for k in AVG_SETTINGS} if saved else None,))
-    if current is not None:
-        for k in AVG_SETTINGS:
-            if saved.get(k) != current.get(k):
-                raise ValueError('--resume: the snapshot was taken with avg_weights %s = %r, this run has %r' % (k, saved.get(k), current.get(k)))
-
-
 GUARD_PREFIX = 'guard/'         # the state word of the guarded step (ramdsir/guard.py named_ranges)
 GUARD_SETTINGS = ('max_norm',)
 
 
+def _compare_ranged(state, current, key, prefix, fields, noun, a_noun, flags):
+    """The rule of a stage that brings ranges of its own (`prefix`) and a record of settings (meta[key], `fields`): ValueError naming
+    `key` where the file has no such ranges and the run wants them, has them and the run does not, or was taken under other settings.
+    noun / a_noun: what the ranges hold, without and with its article; flags: the command-line flags that switch the stage on."""
+    saved = (state.get('meta') or {}).get(key)
+    has = any(e['name'].startswith(prefix) for e in state['table'])
+    if current is not None and not (has and saved):
+        raise ValueError('--resume: the snapshot holds no %s (it was taken without %s); this run has %s = %r' % (noun, flags, key, dict(current)))
+    if current is None and (has or saved):
+        raise ValueError('--resume: the snapshot holds %s (%s = %r); this run was started without %s'
+                         % (a_noun, key, {k: saved.get(k) for k in fields} if saved else None, flags))
+    if current is not None:
+        for k in fields:
+            if saved.get(k) != current.get(k):
+                raise ValueError('--resume: the snapshot was taken with %s %s = %r, this run has %r' % (key, k, saved.get(k), current.get(k)))
+
+
+def compare_avg_weights(state, current):
+    """--resume with / without --avg_weights.  current: the run's settings (avg.WeightAverage.settings()) or None when the flag is off.
+    An average cannot be made up, dropped or continued under another rule in the middle of a run."""
+    _compare_ranged(state, current, 'avg_weights', AVG_PREFIX, AVG_SETTINGS, 'averaged model', 'an averaged model', '--avg_weights')
+
+
 def compare_grad_guard(state, current):
     """--resume with / without --clip_grad_norm / --skip_nonfinite.  current: the run's settings (guard.GradGuard.settings()) or None
-    when the guard is off.  ValueError naming grad_guard where the file has no guard state and the run wants one, has one and the run
-    does not, or was taken under another max_norm: the count of skipped steps shapes Adam's bias corrections and cannot be made up or
-    dropped, and a changed clipping norm is another optimizer in the middle of a run."""
-    saved = (state.get('meta') or {}).get('grad_guard')
-    has = any(e['name'].startswith(GUARD_PREFIX) for e in state['table'])
-    if current is not None and not (has and saved):
-        raise ValueError('--resume: the snapshot holds no guard state (it was taken without --clip_grad_norm / --skip_nonfinite); this run '
-                         'has grad_guard = %r' % (dict(current),))
-    if current is None and (has or saved):
-        raise ValueError('--resume: the snapshot holds a guard state (grad_guard = %r); this run was started without --clip_grad_norm / '
-                         '--skip_nonfinite' % ({k: saved.get(k) for k in GUARD_SETTINGS} if saved else None,))
-    if current is not None:
-        for k in GUARD_SETTINGS:
-            if saved.get(k) != current.get(k):
-                raise ValueError('--resume: the snapshot was taken with grad_guard %s = %r, this run has %r' % (k, saved.get(k), current.get(k)))
+    when the guard is off.  The count of skipped steps shapes Adam's bias corrections and cannot be made up or dropped, and a changed
+    clipping norm is another optimizer in the middle of a run."""
+    _compare_ranged(state, current, 'grad_guard', GUARD_PREFIX, GUARD_SETTINGS, 'guard state', 'a guard state',
+                    '--clip_grad_norm / --skip_nonfinite')
 
 
 def compare_optim(state, current):

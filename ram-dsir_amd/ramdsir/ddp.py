@@ -49,9 +49,9 @@ class GradBuckets:
 
 class DataParallelStep:
     """Wraps a TrainStep: four hipGraphs (segments A, B1, B2, C) with the three all-reduces between them.
-    With TrainStep.enable_grad_guard the eager step runs the guarded tail (ramdsir/guard.py) in place of segment C; captured graphs
-    are refused.  No multi-rank run of the guarded step has been made: its test runs a single-rank group.  TrainStep.enable_optim
-    (ramdsir/optim.py) gets the same treatment: rd_optim_step and the repack in place of segment C, under the guard where both are on."""
+    With TrainStep.enable_grad_guard and / or enable_optim the eager step runs TrainStep.enqueue_tail (ramdsir/step.py) in place of
+    segment C; captured graphs are refused, and so is gradient accumulation.  No multi-rank run of such a step has been made: the
+    tests run a single-rank group."""
 
     def __init__(self, ts, group=None):
         self.ts = ts
@@ -156,10 +156,7 @@ class DataParallelStep:
 
     def capture(self):
         ts = self.ts
-        if ts._guard is not None:
-            raise RuntimeError('DataParallelStep.capture() records segment C: the guarded tail (enable_grad_guard) is not part of it')
-        if ts._optim is not None:
-            raise RuntimeError('DataParallelStep.capture() records segment C: the grouped Adam (enable_optim) is not part of it')
+        ts.refuse_fixed_list('DataParallelStep.capture()')
         ts._refuse_budgets_on_one_chain('DataParallelStep.capture()')
         ts.wpack.refresh(ts._stream())
         torch.cuda.synchronize()
@@ -204,10 +201,8 @@ class DataParallelStep:
             raise RuntimeError('captured graphs replay the classical step on input slot 0: do not mix them with load_raw_next()')
         if self.graphs is not None and self.ts._after_step is not None:
             raise RuntimeError('captured graphs replay a fixed launch list: nothing can be armed behind their step')
-        if self.graphs is not None and self.ts._guard is not None:
-            raise RuntimeError('captured graphs replay a fixed launch list: the guarded tail cannot replace their segment C')
-        if self.graphs is not None and self.ts._optim is not None:
-            raise RuntimeError('captured graphs replay a fixed launch list: the grouped Adam cannot replace their segment C')
+        if self.graphs is not None:
+            self.ts.refuse_fixed_list('DataParallelStep.step() behind capture()')
         # segment -> bucket that is complete when it ends: A -> decoders (2), B1 -> deep encoder (1), B2 -> shallow (0)
         plan = ((0, 2), (1, 1), (2, 0))
         if self.graphs is not None:
@@ -239,17 +234,13 @@ class DataParallelStep:
             if w is not None:
                 w.wait()
         main.wait_stream(self.comm)
-        if self.ts._guard is not None:
-            # the guarded tail in place of segment C (ramdsir/guard.py): behind the exchange the gradients are bit-identical on every
-            # rank, so every rank takes the same decision with no collective.  (No multi-rank run of this path has been made: it is
-            # tested on a single-rank group.)
-            self.ts._guard.enqueue_tail(main.cuda_stream)
-        elif self.ts._optim is not None:
-            # the grouped Adam in place of segment C (ramdsir/optim.py): identical gradients on every rank, no collective.  (Tested on
-            # a single-rank group only, like the guarded tail.)
-            self.ts.enqueue_optim_tail(main.cuda_stream)
-        else:
+        if not self.ts._tail_stages():
             self._run(3, main)
+        else:
+            # TrainStep.enqueue_tail in place of segment C: behind the exchange the gradients are bit-identical on every rank, so every
+            # rank's guard takes the same decision and every rank's Adam the same step with no collective.  (No multi-rank run of this
+            # path has been made: it is tested on a single-rank group.)
+            self.ts.enqueue_tail(main.cuda_stream)
         if self.graphs is None:
             self.ts.run_after_step()
             self.ts.advance()

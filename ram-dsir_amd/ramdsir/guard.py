@@ -7,12 +7,12 @@ BatchNorm buffer the forward pass has moved is rolled back, Adam's bias correcti
 still advances (the reference's lr is a function of iter_num, code/train.py:289).
 
 Everything is decided on the device: the launches communicate through one 40-byte state word (rd_guard_state_t), every launch argument
-is the same at every step, and the host reads the word only where it synchronises anyway.  The op table of the native launch list is
-ABI, so the guarded tail is NOT part of a launch list: TrainStep.step() ends its native call at the encoder backward with every lane
-joined and enqueues the tail from here, on the main stream.
+is the same at every step, and the host reads the word only where it synchronises anyway.  The guard owns its own two calls only:
+TrainStep.enqueue_tail (ramdsir/step.py: the one place that says where the native call is cut and in which order the tail runs) puts
+the verdict in front of Adam and the sync behind the weight repack, and hands Adam the state word.
 
-    GradGuard.enqueue_tail(stream)   rd_grad_guard, rd_adam_step_guarded (rd_optim_step with the state word where the trainer's
-                                     grouped Adam is enabled, ramdsir/optim.py), the weight repack, rd_guard_sync: six launches
+    GradGuard.enqueue_verdict(stream)   rd_grad_guard: norm, scale and skip into the state word
+    GradGuard.enqueue_sync(stream)   rd_guard_sync: the roll-back of the BatchNorm buffers or the refresh of their shadows
     GradGuard.read()                 the state word as a dict (synchronises)
     GradGuard.sync_shadow()          shadow <- live, outside the step (at enable time, after a restore)
     model(grad, max_norm, state)     the numpy model of rd_grad_guard's two launches, in their summation order
@@ -163,14 +163,14 @@ def run_sync(arr, table_dev, n, chunks, state_ptr, stream=None):
 
 
 class GradGuard:
-    """The state word, the workspace, the shadow copies of the BatchNorm buffers with their range table, and the guarded tail of a
-    FusedTrainer's step.  max_norm 0: the guard without clipping (--skip_nonfinite alone).  An active guard always skips non-finite
+    """The state word, the workspace, the shadow copies of the BatchNorm buffers with their range table, and the two calls they serve in
+    the tail of a FusedTrainer's step.  max_norm 0: the guard without clipping (--skip_nonfinite alone).  An active guard always skips non-finite
     steps.  Data parallel: the gradients are bit-identical on every rank behind the exchange, so every rank takes the same decision
     without a collective; the shadows are rank-local like the buffers they copy."""
 
     def __init__(self, trainer, max_norm=0.0):
         self.trainer, self.max_norm = trainer, check_max_norm(max_norm)
-        self.bank, self.ts = bank, ts = trainer.bank, trainer.ts
+        self.bank = bank = trainer.bank
         if bank.n > L.GUARD_MAX_N:
             raise ValueError('grad guard: an arena of %d elements (rd_grad_guard takes up to %d)' % (bank.n, L.GUARD_MAX_N))
         dev = bank.device
@@ -199,17 +199,13 @@ class GradGuard:
         for _, live, shadow in self.ranges:
             shadow.copy_(live)
 
-    def enqueue_tail(self, stream):
-        """The step's tail behind whatever `stream` holds (the encoder backward, every lane joined): the verdict, Adam under it, the
-        weight repack (of unchanged parameters behind a skipped step), the roll-back or the refresh of the shadows."""
-        lib, st = L.lib(), self.state.data_ptr()
-        L.check(lib.rd_grad_guard(C.byref(self.desc), stream), 'rd_grad_guard')
-        if self.ts._optim is not None:                              # TrainStep.enable_optim: the grouped Adam under the same state word
-            self.ts._optim.enqueue(stream, st)
-        else:
-            L.check(lib.rd_adam_step_guarded(C.byref(self.ts.ad), st, stream), 'rd_adam_step_guarded')
-        self.ts.wpack.refresh(stream)
-        L.check(lib.rd_guard_sync(self.arr, self.table_dev.data_ptr(), self.n, self.chunks, st, stream), 'rd_guard_sync')
+    def enqueue_verdict(self, stream):
+        """The verdict on the gradient arena as `stream` (a raw stream handle) leaves it, into the state word: norm, scale, skip."""
+        L.check(L.lib().rd_grad_guard(C.byref(self.desc), stream), 'rd_grad_guard')
+
+    def enqueue_sync(self, stream):
+        """Behind Adam and the repack: the roll-back of the BatchNorm buffers (a skipped step) or the refresh of the shadows."""
+        L.check(L.lib().rd_guard_sync(self.arr, self.table_dev.data_ptr(), self.n, self.chunks, self.state.data_ptr(), stream), 'rd_guard_sync')
 
     def read(self):
         """The state word as a dict: norm, scale, skip, nonfinite of the last step; steps, clipped, skipped so far.  Synchronises."""

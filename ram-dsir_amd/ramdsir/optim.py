@@ -8,9 +8,8 @@ reference's optimizer is the two-range special case of this table, bit for bit.
 The decay rule: tensors with more than one dimension (the convolution kernels) decay; 1-D tensors (biases, BatchNorm weight and bias)
 are exempt.
 
-The op table of the native launch list is ABI, so the grouped step is NOT part of a launch list: TrainStep.step() ends its native
-call at the encoder backward with every lane joined, and the optimizer and the weight repack follow as direct calls on the main
-stream (as the guarded tail does, ramdsir/guard.py; with both enabled the guard calls rd_optim_step under its state word).
+The grouped step is not part of a launch list: it is the Adam of TrainStep.enqueue_tail (ramdsir/step.py, which says where the native
+call is cut and in which order the tail runs), under the guard's state word where the guard (ramdsir/guard.py) is on as well.
 
     build_table(bank, enc_lr_mult, weight_decay)        the rd_optim_range_t array of a ParamBank (CPU or GPU) and its chunk count
     make_table(entries)                                 the same from [(first, count, lr_mult, weight_decay)]
@@ -164,6 +163,6 @@ class GroupedAdam:
 
     def enqueue(self, stream, guard_state_ptr=None):
         """The optimizer step behind whatever `stream` holds: the prepare launch and the update launch; under a guard's state word
-        (guard.GradGuard.enqueue_tail) with its scale, its skip and its count of applied updates."""
+        (TrainStep.enqueue_tail hands it over) with its scale, its skip and its count of applied updates."""
         L.check(L.lib().rd_optim_step(C.byref(self.desc), self.arr, self.table_dev.data_ptr(), self.n, self.chunks, guard_state_ptr, stream),
                 'rd_optim_step')

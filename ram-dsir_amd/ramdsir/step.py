@@ -7,7 +7,9 @@ launch list on one HIP stream, optionally captured into a hipGraph:
               -> seg-decoder backward -> rec-decoder backward -> encoder backward
               -> Adam (3 param groups, poly LR) -> repack conv weights
 
-Only the flag combination that runs in the reference (--ram --rec [--consistency]) exists here.
+Only the flag combination that runs in the reference (--ram --rec [--consistency]) exists here.  With gradient accumulation, the
+guard or the grouped Adam enabled (accum.py, guard.py, optim.py) the last line is TrainStep.enqueue_tail: direct calls behind a
+native call that ends at the encoder backward.
 """
 import ctypes as C
 import os
@@ -19,6 +21,12 @@ from . import engine as E
 from . import ram as R
 from . import streams
 from . import tuning as T
+
+
+# the optional stages of the step's tail (TrainStep.enqueue_tail): the slot of each and what a refusal calls it, in the order refusals
+# name them
+TAIL_STAGES = (('_guard', 'the guarded tail (enable_grad_guard)'), ('_optim', 'the grouped Adam (enable_optim)'),
+               ('_accum', 'gradient accumulation (enable_grad_accum)'))
 
 
 class TrainStep:
@@ -403,12 +411,7 @@ class TrainStep:
 
     def capture(self):
         """Capture one step (zeroing + every launch) into a hipGraph on a side stream."""
-        if self._guard is not None:
-            raise RuntimeError('capture() records the classical step: the guarded tail (enable_grad_guard) is not part of a launch list')
-        if self._optim is not None:
-            raise RuntimeError('capture() records the classical step: the grouped Adam (enable_optim) is not part of a launch list')
-        if self._accum is not None:
-            raise RuntimeError('capture() records the classical step: gradient accumulation (enable_grad_accum) is not part of a launch list')
+        self.refuse_fixed_list('capture()')
         self._refuse_budgets_on_one_chain('capture()')
         self.wpack.refresh(self._stream())
         torch.cuda.synchronize()
@@ -458,63 +461,74 @@ class TrainStep:
                 raise RuntimeError('a captured hipGraph replays a fixed launch list: nothing can be armed behind its step')
             self.graph.replay()
             return
-        if self._accum is not None:
-            # gradient accumulation (ramdsir/accum.py) takes the same cut: the native call ends at the encoder backward with every
-            # lane joined, rd_grad_accum follows, and only the window's last micro-batch is followed by the tail that applies
-            self.launch(self.head_names() + self.backward_names(), join=True)
-            stream = torch.cuda.current_stream().cuda_stream
-            if self._accum.enqueue(stream):
-                if self._guard is not None:
-                    self._guard.enqueue_tail(stream)
-                elif self._optim is not None:
-                    self.enqueue_optim_tail(stream)
-                else:
-                    L.check(L.lib().rd_adam_step(C.byref(self.ad), stream), 'rd_adam_step')
-                    self.wpack.refresh(stream)
-        elif self._guard is not None:
-            # the guarded tail is not in the op table of the launch list: the native call ends at the encoder backward with every
-            # lane joined, and Adam + repack follow as direct calls on the main stream (ramdsir/guard.py; with enable_optim its
-            # Adam is rd_optim_step under the guard's state word)
-            self.launch(self.head_names() + self.backward_names(), join=True)
-            self._guard.enqueue_tail(torch.cuda.current_stream().cuda_stream)
-        elif self._optim is not None:
-            # the grouped Adam is not in the op table either: the same cut, then rd_optim_step and the repack (ramdsir/optim.py)
-            self.launch(self.head_names() + self.backward_names(), join=True)
-            self.enqueue_optim_tail(torch.cuda.current_stream().cuda_stream)
-        else:
+        if not self._tail_stages():
             self.launch(self.head_names() + self.backward_names() + ('seg_c',), join_before_last=True)
+        else:
+            self.launch(self.head_names() + self.backward_names(), join=True)
+            self.enqueue_tail(torch.cuda.current_stream().cuda_stream)
         self.run_after_step()
         self.advance()
 
-    def enable_grad_guard(self, guard):
-        """From now on step() runs guard.enqueue_tail (rd_grad_guard, rd_adam_step_guarded, the repack, rd_guard_sync) in place of
-        seg_c.  A captured hipGraph replays a fixed launch list: refused."""
+    def enqueue_tail(self, stream):
+        """The optimizer tail of the step as direct calls on `stream` (a raw stream handle), behind whatever it holds -- the encoder
+        backward with every lane joined -- in the one order there is: accumulate, verdict, Adam, repack, sync.  The op table of the
+        native launch list is ABI and seg_c is its classical tail (rd_adam_step + repack), so a step with any stage of TAIL_STAGES
+        enabled CUTS its native call at the encoder backward (step(); ddp.DataParallelStep.step() behind its bucket waits) and
+        enqueues from here:
+          1. _accum.enqueue (rd_grad_accum, ramdsir/accum.py); within an open window nothing else follows: returns False
+          2. _guard.enqueue_verdict (rd_grad_guard, ramdsir/guard.py)
+          3. Adam: _optim.enqueue (rd_optim_step, ramdsir/optim.py) under the guard's state word where there is one; without the
+             grouped Adam rd_adam_step_guarded under a guard, rd_adam_step otherwise
+          4. the weight repack (of unchanged parameters behind a step the guard skips)
+          5. _guard.enqueue_sync (rd_guard_sync)
+        Returns True where the optimizer ran."""
+        if self._accum is not None and not self._accum.enqueue(stream):
+            return False
+        guard = self._guard
+        state = guard.state.data_ptr() if guard is not None else None
+        if guard is not None:
+            guard.enqueue_verdict(stream)
+        if self._optim is not None:
+            self._optim.enqueue(stream, state)
+        elif guard is not None:
+            L.check(L.lib().rd_adam_step_guarded(C.byref(self.ad), state, stream), 'rd_adam_step_guarded')
+        else:
+            L.check(L.lib().rd_adam_step(C.byref(self.ad), stream), 'rd_adam_step')
+        self.wpack.refresh(stream)
+        if guard is not None:
+            guard.enqueue_sync(stream)
+        return True
+
+    def _tail_stages(self):
+        """The descriptions of the enabled stages of enqueue_tail, in the order of TAIL_STAGES."""
+        return [text for slot, text in TAIL_STAGES if getattr(self, slot) is not None]
+
+    def refuse_fixed_list(self, what, stages=None):
+        """RuntimeError naming `stages` (default: the enabled ones) if there are any: a captured hipGraph replays a fixed launch
+        list, and the stages of enqueue_tail are direct calls behind a cut native call."""
+        stages = self._tail_stages() if stages is None else stages
+        if stages:
+            raise RuntimeError('%s: a captured hipGraph replays a fixed launch list, which has no place for %s' % (what, ', '.join(stages)))
+
+    def _enable(self, slot, stage):
         if self.graph is not None:
-            raise RuntimeError('a captured hipGraph replays a fixed launch list: the guarded tail cannot replace its Adam')
-        self._guard = guard
+            self.refuse_fixed_list('this step has been captured', [dict(TAIL_STAGES)[slot]])
+        setattr(self, slot, stage)
+
+    def enable_grad_guard(self, guard):
+        """From now on step() runs enqueue_tail with the verdict and the sync of `guard` around a guarded Adam.  Refused behind
+        capture()."""
+        self._enable('_guard', guard)
 
     def enable_optim(self, optim):
-        """From now on step() runs optim.enqueue (rd_optim_step: the grouped Adam of ramdsir/optim.py) and the weight repack as direct
-        calls in place of seg_c -- under the guard's state word where enable_grad_guard is on as well.  The launch list's op table
-        and seg_c stay as they are.  A captured hipGraph replays a fixed launch list: refused."""
-        if self.graph is not None:
-            raise RuntimeError('a captured hipGraph replays a fixed launch list: the grouped Adam cannot replace its Adam')
-        self._optim = optim
+        """From now on step() runs enqueue_tail with optim.enqueue (the grouped Adam) as its Adam.  Refused behind capture()."""
+        self._enable('_optim', optim)
 
     def enable_grad_accum(self, accum):
-        """From now on step() ends its native call at the encoder backward, runs accum.enqueue (rd_grad_accum, ramdsir/accum.py) and
-        only at the last micro-batch of a window the tail that applies: guard.enqueue_tail where enable_grad_guard is on,
-        enqueue_optim_tail where enable_optim is on, otherwise rd_adam_step and the weight repack as direct calls.  The launch list's
-        op table and seg_c stay as they are; the per-step rd_zero, the pipelined RAM of the next batch and the input slots are
-        untouched.  A captured hipGraph replays a fixed launch list: refused."""
-        if self.graph is not None:
-            raise RuntimeError('a captured hipGraph replays a fixed launch list: gradient accumulation cannot cut its step')
-        self._accum = accum
-
-    def enqueue_optim_tail(self, stream):
-        """The unguarded tail with enable_optim: the grouped Adam, then the weight repack, on `stream` (a raw stream handle)."""
-        self._optim.enqueue(stream, None)
-        self.wpack.refresh(stream)
+        """From now on step() runs enqueue_tail with accum.enqueue in front: the rest of the tail follows at a window's last
+        micro-batch only.  The per-step rd_zero, the pipelined RAM of the next batch and the input slots are untouched.  Refused
+        behind capture()."""
+        self._enable('_accum', accum)
 
     def loss_dict(self):
         """Synchronises.  Names follow the tensorboard scalars of train.py:298-304."""

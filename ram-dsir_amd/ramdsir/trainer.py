@@ -73,13 +73,21 @@ class FusedTrainer:
         self._primed = pipelined
         self._announced = tuple(next_batch[:4]) if pipelined else None
 
+    def _refuse_graphs(self, what):
+        if self._graphs:
+            raise RuntimeError('%s: a captured hipGraph replays a fixed launch list (use_graph=True)' % what)
+
+    def stages(self):
+        """(avg, guard, optim, accum): what enable_avg_weights, enable_grad_guard, enable_optim and enable_grad_accum have returned,
+        None where one is off -- in the order their records and ranges go into a training-state snapshot (train.py open_state)."""
+        return self._avg, self._guard, self._optim, self._accum
+
     def arm_tb_images(self):
         """The next step() also composes the TensorBoard image grids of ITS batch (ramdsir/tb_images.py; code/train.py:306-329,
         475-496) and starts their copy to pinned host memory; take_tb_images() then returns the pending result.  The compose is
         enqueued behind the step's last launch and in front of the upload of the next mask (TrainStep.arm_after_step), reads the
         input slot the step trained on, and only reads: training is bit-identical with and without it.  Not with use_graph=True."""
-        if self._graphs:
-            raise RuntimeError('arm_tb_images: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        self._refuse_graphs('arm_tb_images')
         from . import tb_images
         ts = self.ts
         if self._tb is None:
@@ -117,8 +125,7 @@ class FusedTrainer:
         sits on the main stream behind the step's last launch (TrainStep.arm_after_step), reads the device-side iteration counter
         itself and only reads the trainer's buffers: training is bit-identical with and without it.  Data parallel: rank-local, no
         collective.  Returns the avg.WeightAverage.  Not with use_graph=True."""
-        if self._graphs:
-            raise RuntimeError('enable_avg_weights: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        self._refuse_graphs('enable_avg_weights')
         from . import avg
         self._avg = avg.WeightAverage(self, mode, decay, start)
         return self._avg
@@ -130,8 +137,7 @@ class FusedTrainer:
         HERE from the live buffers).  Decided on the device, no read-back.  The after-step launches (step log, averaging, image grids)
         run behind the guarded tail as behind Adam; the gradient arena is never modified.  Returns the guard.GradGuard.  Not with
         use_graph=True."""
-        if self._graphs:
-            raise RuntimeError('enable_grad_guard: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        self._refuse_graphs('enable_grad_guard')
         from . import guard
         self._guard = guard.GradGuard(self, max_norm)
         self.ts.enable_grad_guard(self._guard)
@@ -143,10 +149,9 @@ class FusedTrainer:
         decay (weight_decay on tensors with more than one dimension -- the conv kernels; biases and BatchNorm weight / bias are
         exempt), decoupled (AdamW) or L2 (Adam(weight_decay)); the schedule (poly with the reference's lag, cosine, constant) and a
         linear warm-up are evaluated on the device from the counter.  The default values give the reference's optimizer, bit for
-        bit.  Counter, schedule words and lr() are rd_adam_step's; with enable_grad_guard (in either order) the guard's tail calls it
-        under its state word.  Returns the optim.GroupedAdam.  Not with use_graph=True."""
-        if self._graphs:
-            raise RuntimeError('enable_optim: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        bit.  Counter, schedule words and lr() are rd_adam_step's; with enable_grad_guard (in either order) the step's tail
+        (TrainStep.enqueue_tail) calls it under the guard's state word.  Returns the optim.GroupedAdam.  Not with use_graph=True."""
+        self._refuse_graphs('enable_optim')
         from . import optim
         self._optim = optim.GroupedAdam(self, weight_decay, wd_mode, lr_schedule, warmup_iters, enc_lr_mult)
         self.ts.enable_optim(self._optim)
@@ -163,8 +168,7 @@ class FusedTrainer:
         with use_graph=True, not data parallel."""
         from . import accum
         steps = accum.check_steps(steps)
-        if self._graphs:
-            raise RuntimeError('enable_grad_accum: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        self._refuse_graphs('enable_grad_accum')
         if self.world > 1:
             raise RuntimeError('enable_grad_accum: gradient accumulation runs in one process (the bucketed gradient exchange of %d ranks '
                                'is tied to the segments of the step)' % self.world)
@@ -182,8 +186,7 @@ class FusedTrainer:
         the join of all lanes, Adam and the repack, in front of the upload of the next mask (TrainStep.arm_after_step) -- and only
         reads the step's buffers: training is bit-identical with and without it.  drain_step_log() returns the records.  Not with
         use_graph=True."""
-        if self._graphs:
-            raise RuntimeError('enable_step_log: a captured hipGraph replays a fixed launch list (use_graph=True)')
+        self._refuse_graphs('enable_step_log')
         from . import step_log
         ts, b = self.ts, self.bank
         r = [b.module_range['enc'][0], b.module_range['enc'][1], b.module_range['dec'][1], b.module_range['rec'][1]]

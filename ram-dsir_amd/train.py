@@ -841,9 +841,19 @@ def init_process(world, local):
     return dist.new_group(backend='gloo') if world > 1 else None
 
 
-def open_state(args, trainer, fingerprint_args, resume_state, avg=None, guard=None, optim=None, accum=None):
+def state_meta(trainer):
+    """What the enabled stages of the trainer (FusedTrainer.stages()) record in a snapshot's meta, under their keys."""
+    avg, guard, optim, accum = trainer.stages()
+    meta = {key: obj.settings() for key, obj in (('avg_weights', avg), ('grad_guard', guard), ('optim', optim)) if obj is not None}
+    if accum is not None:                               # an odd epoch length leaves a window open across the epoch boundary
+        meta['grad_accum'] = dict(accum.settings(), micro=accum.position())
+    return meta
+
+
+def open_state(args, trainer, fingerprint_args, resume_state):
     """--ckpt_every / --resume, device side: the trainer's ranges, the staging buffers and the writer thread, once (ramdsir/ckpt.py);
     --resume: the arenas, the BatchNorm buffers and the schedule counter from the file (restore_host_side follows before the loop).
+    What is enabled is read off the trainer (FusedTrainer.stages()):
     avg (--avg_weights): the averaged model's ranges go behind the trainer's; a file and a run that disagree about them are refused.
     guard (--clip_grad_norm / --skip_nonfinite): its state word goes behind those, under the same rule; behind a restore its shadow
     copies are taken from the restored BatchNorm buffers.  optim (the five optimizer flags): no range of its own -- its state is the
@@ -853,12 +863,12 @@ def open_state(args, trainer, fingerprint_args, resume_state, avg=None, guard=No
     hold the BatchNorm buffers of the window's START; a file taken under another N (without the record: N = 1) is refused; the restore
     sets the host-side position in the window."""
     from ramdsir import ckpt
-    micro = 0
+    (avg, guard, _, accum), current, micro = trainer.stages(), state_meta(trainer), 0
     if resume_state is not None:
-        ckpt.compare_avg_weights(resume_state, avg.settings() if avg is not None else None)
-        ckpt.compare_grad_guard(resume_state, guard.settings() if guard is not None else None)
-        ckpt.compare_optim(resume_state, optim.settings() if optim is not None else None)
-        micro = ckpt.compare_grad_accum(resume_state, accum.settings() if accum is not None else None)
+        ckpt.compare_avg_weights(resume_state, current.get('avg_weights'))
+        ckpt.compare_grad_guard(resume_state, current.get('grad_guard'))
+        ckpt.compare_optim(resume_state, current.get('optim'))
+        micro = ckpt.compare_grad_accum(resume_state, current.get('grad_accum'))
     extra = (avg.named_ranges() if avg is not None else []) + (guard.named_ranges() if guard is not None else [])
     if accum is not None:
         extra += (guard.shadow_ranges() if guard is not None else []) + accum.named_ranges()
@@ -942,13 +952,13 @@ def main(args):
     # --clip_grad_norm / --skip_nonfinite: the guarded tail replaces Adam + repack in the step; the shadows copy the initial buffers
     guard = trainer.enable_grad_guard(guard_max_norm(args)) if uses_guard(args) else None
     # the five optimizer flags: the grouped Adam replaces rd_adam_step in the step (under the guard's state word where both are on)
-    optim = enable_optim(args, trainer, total_iters, rank) if uses_optim(args) else None
+    if uses_optim(args):
+        enable_optim(args, trainer, total_iters, rank)
     # --accum_steps: one rd_grad_accum launch behind every backward pass, the tail above behind every N-th (total_iters counts updates)
     accum = trainer.enable_grad_accum(args.accum_steps) if uses_accum(args) else None
     if accum is not None and rank == 0:
         print(accum_line(args.accum_steps, *accum_totals(args, max_len)))
-    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state, avg, guard, optim, accum) \
-        if uses_ckpt(args) else None
+    state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state) if uses_ckpt(args) else None
     if val is not None:
         val.bind(trainer)
         if avg is not None and val.mode != 'fused':
@@ -996,17 +1006,11 @@ def main(args):
             meta = dict(
                 epoch=epoch, iter_num=iter_num, previous_best=previous_best, rng=ckpt.host_rng_state(),
                 cycles=[None if it is dl else it.state() for it, dl in zip(loaders, raw)],
-                val_log_bytes=os.path.getsize(val_log_path(args)) if os.path.exists(val_log_path(args)) else 0)
+                val_log_bytes=os.path.getsize(val_log_path(args)) if os.path.exists(val_log_path(args)) else 0, **state_meta(trainer))
             if avg is not None:
                 avg_log = val_log_path(args, '_avg')
-                meta['avg_weights'] = dict(avg.settings(), previous_best_avg=previous_best_avg,
+                meta['avg_weights'].update(previous_best_avg=previous_best_avg,
                                            val_log_bytes=os.path.getsize(avg_log) if os.path.exists(avg_log) else 0)
-            if guard is not None:
-                meta['grad_guard'] = guard.settings()
-            if optim is not None:
-                meta['optim'] = optim.settings()
-            if accum is not None:                       # an odd epoch length leaves a window open across the epoch boundary
-                meta['grad_accum'] = dict(accum.settings(), micro=accum.position())
             state_io.snapshot(osp.join(args.save_path, 'last_state.pth'), meta)
         if rank == 0:
             t_all, n_img = time.time() - t_epoch, (iter_num - it_epoch) * log.imgs_per_iter

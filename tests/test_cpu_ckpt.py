@@ -9,17 +9,17 @@ import os
 import pickle
 import random
 import subprocess
-import types
 
 import numpy as np
 import pytest
 import torch
 
 import synth_data as SD
+from fake_trainer import fake_state as _fake_state, fake_trainer as _fake_trainer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-from ramdsir import _lib as L, ckpt as CK, engine as E       # noqa: E402
+from ramdsir import _lib as L, ckpt as CK       # noqa: E402
 
 M64 = 1 << 64
 
@@ -124,32 +124,6 @@ def test_replay_cycle_state_raises_during_the_first_pass_only():
 
 
 # ------------------------------------------------------------------------------------------------------------- the file
-def _fake_trainer(seed=3):
-    """What ckpt reads of a FusedTrainer, on the CPU: the bank with Adam moments, iter / hyper, the modules' specs."""
-    mods = [('enc', E.encoder_specs()), ('dec', E.decoder_specs()), ('rec', E.rec_decoder_specs(16, 3, 3))]
-    bank = E.ParamBank(mods, 'cpu')
-    bank.ensure_adam()
-    g = torch.Generator().manual_seed(seed)
-    for t in (bank.params, bank.exp_avg, bank.exp_avg_sq):
-        t.copy_(torch.randn(t.shape, generator=g))
-    for k, t in bank.buffers.items():
-        t.copy_(torch.randint(1, 1000, t.shape, generator=g).to(t.dtype))
-    ts = types.SimpleNamespace(iter=torch.tensor(41, dtype=torch.int32), hyper=torch.tensor([2e-3, 0.5, 1e-3, 41.0]), dtype=torch.bfloat16)
-    modules = {m: types.SimpleNamespace(_specs=s) for m, s in mods}
-    return types.SimpleNamespace(bank=bank, ts=ts, modules=modules)
-
-
-def _fake_state(tr, meta=None):
-    named = CK.trainer_ranges(tr)
-    table, total = CK.layout(named)
-    blob = torch.zeros(total, dtype=torch.uint8)
-    for (name, t), e in zip(named, table):
-        raw = t.contiguous().view(-1).view(torch.uint8) if t.dim() else t.reshape(1).view(torch.uint8)
-        blob[e['offset']:e['offset'] + e['bytes']] = raw
-        e['s1'], e['s2'] = CK.checksums(raw.numpy())
-    return CK.make_state(table, blob, meta or dict(epoch=1, iter_num=41, previous_best=12.5), dict(manifest=CK.trainer_manifest(tr)))
-
-
 @pytest.fixture(scope='module')
 def fake():
     tr = _fake_trainer()

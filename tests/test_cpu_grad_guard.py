@@ -16,7 +16,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-from ramdsir import _lib as L, ckpt as CK, engine as E, guard as G       # noqa: E402
+from ramdsir import _lib as L, ckpt as CK, guard as G       # noqa: E402
+from fake_trainer import fake_state as _fake_state, fake_trainer as _fake_trainer       # noqa: E402
 
 F32 = np.float32
 
@@ -163,21 +164,6 @@ def test_model_over_chunks_and_alignments():
 
 
 # ------------------------------------------------------------------------------------------------------------- the table
-def _fake_trainer(seed=3):
-    """What guard and ckpt read of a FusedTrainer, on the CPU (as tests/test_cpu_ckpt.py)."""
-    mods = [('enc', E.encoder_specs()), ('dec', E.decoder_specs()), ('rec', E.rec_decoder_specs(16, 3, 3))]
-    bank = E.ParamBank(mods, 'cpu')
-    bank.ensure_adam()
-    g = torch.Generator().manual_seed(seed)
-    for t in (bank.params, bank.exp_avg, bank.exp_avg_sq):
-        t.copy_(torch.randn(t.shape, generator=g))
-    for k, t in bank.buffers.items():
-        t.copy_(torch.randint(1, 1000, t.shape, generator=g).to(t.dtype))
-    ts = types.SimpleNamespace(iter=torch.tensor(41, dtype=torch.int32), hyper=torch.tensor([2e-3, 0.5, 1e-3, 41.0]), dtype=torch.bfloat16)
-    modules = {m: types.SimpleNamespace(_specs=s) for m, s in mods}
-    return types.SimpleNamespace(bank=bank, ts=ts, modules=modules)
-
-
 @pytest.fixture(scope='module')
 def fake():
     tr = _fake_trainer()
@@ -307,17 +293,6 @@ def test_train_log_reports_and_warns(capsys):
 
 
 # ------------------------------------------------------------------------------------------------------------- the state file
-def _fake_state(tr, gd=None, meta=None):
-    named = CK.trainer_ranges(tr) + (gd.named_ranges() if gd is not None else [])
-    table, total = CK.layout(named)
-    blob = torch.zeros(total, dtype=torch.uint8)
-    for (name, t), e in zip(named, table):
-        raw = t.contiguous().view(-1).view(torch.uint8) if t.dim() else t.reshape(1).view(torch.uint8)
-        blob[e['offset']:e['offset'] + e['bytes']] = raw
-        e['s1'], e['s2'] = CK.checksums(raw.numpy())
-    return CK.make_state(table, blob, meta or dict(epoch=1, iter_num=41, previous_best=12.5), dict(manifest=CK.trainer_manifest(tr)))
-
-
 def _guard_meta(gd):
     return dict(epoch=1, iter_num=41, previous_best=12.5, grad_guard=gd.settings())
 

@@ -16,7 +16,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 from ramdsir import _lib as L, ckpt as CK, engine as E, optim as O       # noqa: E402
-from test_cpu_grad_guard import _fake_state, _fake_trainer, _round_f32, _train_module       # noqa: E402
+from fake_trainer import fake_state as _fake_state, fake_trainer as _fake_trainer       # noqa: E402
+from test_cpu_grad_guard import _round_f32, _train_module       # noqa: E402
 
 F32 = np.float32
 OPT_FIELDS = [n for n, _ in L.RdOptim._fields_]
