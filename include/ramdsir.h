@@ -847,6 +847,42 @@ typedef struct {
 int rd_avg_step(const rd_avg_range_t* table_host, const rd_avg_range_t* table_dev, int n, int64_t total_chunks,
                 const int32_t* iter_dev, int mode, float one_minus_decay, int32_t start, void* stream);
 
+/* BatchNorm re-estimation of the averaged model (train.py --avg_bn_recal, ramdsir/avg_bn.py), csrc/bn_recal.hip: the cumulative
+ * average of the batch statistics of ALL n_sites BatchNorm sites of a forward plan in one launch -- what
+ * torch.optim.swa_utils.update_bn leaves in a BatchNorm with momentum=None.  No reference counterpart.  Called once per batch,
+ * behind the forward launch list of a plan whose finalize launches leave the running statistics alone (rd_bn_fwd_t with
+ * running_mean = running_var = num_batches_tracked = NULL, as for InstanceNorm above; engine.Plan recal_bn), with k = 0, 1, ... the
+ * index of the batch.  Per site and channel c: (s1, s2) = the sums over the first nslots copies of the site's statistic slots,
+ * then the finalize's own arithmetic (csrc/bn_fin.h fwd_stat, contraction off): mean = (float)(s1 / count + conv_bias[c]) -- the
+ * bits of rd_bn_fwd_t.mean of the same launch list --, var = max(s2 / count - (s1 / count)^2, 0) in fp64,
+ * unb = (float)(var * count / (count - 1)) for count > 1, (float)var otherwise.  With x the batch value (mean resp. unb):
+ *     k == 0:  running = x                                       a plain store, the old content is not read
+ *     k > 0:   d = x - running;  t = w * d;  running = running + t      three separately rounded fp32 operations, never an fma;
+ *                                                                w = 1.0f / (float)(k + 1), the division correctly rounded
+ * and num_batches_tracked = k + 1 (int64).  numpy reproduces it bit for bit (ramdsir/avg_bn.py model()).
+ * sites_dev: the table in device memory, uploaded once by the caller; sites_host: the SAME n_sites records, read for validation
+ * only (rd_avg_step's convention: nothing on the device is dereferenced by the host); max_C: the largest C in the table.  Grid:
+ * (blocks over max_C, n_sites), as rd_bn_eval_coeffs'.  Exactly ONE launch on `stream`, through the library's one launch site; no
+ * hipMemcpyAsync / hipMemsetAsync; allocates nothing, synchronises nothing.  Returns, before anything is launched: -1 a null table,
+ * n_sites outside 1 .. RD_BN_RECAL_MAX_SITES or max_C < 1; -2 k < 0; -3 a site with a null stats, running_mean, running_var or
+ * num_batches_tracked, or a misaligned pointer (stats 16, num_batches_tracked 8, the others 4 bytes); -4 a site with C < 1 or
+ * C > max_C; -5 a site whose count is not >= 1 (NaN included); -6 a site whose nslots is not a multiple of 8 in 8 .. RD_STAT_SLOTS;
+ * -7 eps negative or NaN. */
+#define RD_BN_RECAL_MAX_SITES 4096
+typedef struct {
+    const double* stats;            /* [1][RD_STAT_SLOTS][C][2] sum, sum of squares of one statistics group */
+    const float* conv_bias;         /* [C] bias of the producing conv (its sums exclude it) or NULL (rd_up_stats sums y itself) */
+    float* running_mean;            /* [C] */
+    float* running_var;             /* [C] */
+    int64_t* num_batches_tracked;   /* [1] */
+    float count;                    /* elements per channel of a batch: N * H * W */
+    int32_t C;
+    int32_t nslots;                 /* statistic copies the producers used: a multiple of 8 up to RD_STAT_SLOTS */
+    int32_t pad_;
+} rd_bn_recal_site_t;
+int rd_bn_recal(const rd_bn_recal_site_t* sites_host, const rd_bn_recal_site_t* sites_dev, int n_sites, int max_C, int32_t k, float eps,
+                void* stream);
+
 /* Guarded optimizer step (train.py --clip_grad_norm / --skip_nonfinite, ramdsir/guard.py), csrc/guard.hip + csrc/loss.hip: what
  * stands in front of the reference's `loss.backward(); optimizer.step()` (code/train.py:285-287) when the user asks for it -- the
  * gradient of the whole arena is clipped by its global norm (torch.nn.utils.clip_grad_norm_ over the one optimizer), and a step whose

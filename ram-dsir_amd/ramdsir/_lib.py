@@ -166,6 +166,15 @@ class RdAvgRange(C.Structure):
     _fields_ = [('src', vp), ('dst', vp), ('bytes', i64), ('chunk0', i64), ('kind', i32), ('pad_', i32)]
 
 
+BN_RECAL_MAX_SITES = 4096                                           # RD_BN_RECAL_MAX_SITES
+
+
+class RdBnRecalSite(C.Structure):
+    """rd_bn_recal_site_t (include/ramdsir.h): one BatchNorm site of a recal plan, a row of rd_bn_recal's table."""
+    _fields_ = [('stats', fp), ('conv_bias', fp), ('running_mean', fp), ('running_var', fp), ('num_batches_tracked', vp), ('count', f32),
+                ('C', i32), ('nslots', i32), ('pad_', i32)]
+
+
 GUARD_CHUNK = 16384                                                 # RD_GUARD_CHUNK
 GUARD_MAX_N = 1 << 24                                               # elements rd_grad_guard accepts (rd_step_log's bound)
 
@@ -291,6 +300,7 @@ _SIGS = {
     'rd_step_log_workspace': (i64, [i64]),
     'rd_snapshot': (C.c_int, [C.POINTER(RdSnapRange), vp, C.c_int, i64, vp, i64, vp, C.c_int, vp]),
     'rd_avg_step': (C.c_int, [C.POINTER(RdAvgRange), vp, C.c_int, i64, vp, C.c_int, f32, i32, vp]),
+    'rd_bn_recal': (C.c_int, [C.POINTER(RdBnRecalSite), vp, C.c_int, C.c_int, i32, f32, vp]),
     'rd_grad_guard_workspace': (i64, [i64]),
     'rd_grad_guard': (C.c_int, [C.POINTER(RdGradGuard), vp]),
     'rd_adam_step_guarded': (C.c_int, [C.POINTER(RdAdam), vp, vp]),

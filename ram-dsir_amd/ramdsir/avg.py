@@ -4,8 +4,10 @@ iterate from a start iteration on (SWAD's dense averaging).  The reference has n
 model_%.2f.pth from single-iterate Dice figures on the held-out domain (code/train.py:331-350).
 
 The pass only reads the trainer's buffers (parameters, BatchNorm buffers, the device-side iteration counter): the trained model is
-bit-identical with and without it.  BatchNorm running statistics are averaged like parameters, num_batches_tracked is copied; no
-BatchNorm re-estimation pass is made.
+bit-identical with and without it.  BatchNorm running statistics are averaged like parameters, num_batches_tracked is copied.  A
+BatchNorm re-estimation pass is made on request only (train.py --avg_bn_recal K, ramdsir/avg_bn.py): it re-estimates the statistics
+of the averaged encoder and seg decoder from the last K batches of an epoch into a third set of buffers, which the averaged model's
+validation and checkpoints then read; the buffers averaged here, and a training-state snapshot of them, are not touched by it.
 
     WeightAverage.enqueue(stream)   one rd_avg_step call (one launch); every argument is the same at every step
     model(avg, live, s, ...)        the numpy model of the kernel's fp32 arithmetic: bit for bit
@@ -111,10 +113,14 @@ class WeightAverage:
         self.arr, self.chunks = build_table([(a.data_ptr(), b.data_ptr(), a.numel() * a.element_size(), kind) for _, a, b, kind in self.ranges])
         self.table_dev = upload_table(self.arr, self.n, self.live.device)       # once: the pointers never move
         self._forward = {}
+        self.bn_recal = None                    # FusedTrainer.enable_avg_bn_recal: the avg_bn.BnRecal that re-estimates this model's BatchNorm
 
     def settings(self):
-        """What a snapshot records and --resume compares."""
-        return dict(mode=self.mode, decay=self.decay if self.mode == 'ema' else None, start=self.start)
+        """What a snapshot records and --resume compares (bn_recal: the K of --avg_bn_recal, recorded only where the pass is on)."""
+        out = dict(mode=self.mode, decay=self.decay if self.mode == 'ema' else None, start=self.start)
+        if self.bn_recal is not None:
+            out['bn_recal'] = self.bn_recal.settings()
+        return out
 
     def enqueue(self, stream=None):
         """The pass behind whatever `stream` holds: one rd_avg_step call."""
@@ -127,14 +133,20 @@ class WeightAverage:
 
     def state_dicts(self):
         """The reference's three state_dicts of the averaged model: save_checkpoint's keys, each module's entries in its state_dict
-        order with the live model's shapes and dtypes (copies)."""
+        order with the live model's shapes and dtypes (copies).  With --avg_bn_recal the encoder / seg-decoder BatchNorm buffers are the
+        re-estimated ones (avg_bn.BnRecal.state_dicts(): the same keys and order, the same parameters)."""
+        if self.bn_recal is not None:
+            return self.bn_recal.state_dicts()
         from .ckpt import MODULE_KEYS
         from .step import state_dict_of
         return OrderedDict((key, state_dict_of(self.bank, m, self.trainer.modules[m]._specs)) for m, key in MODULE_KEYS)
 
     def eval_forward(self, dtype=None):
         """infer.EvalForward over the averaged bank, one per storage dtype (default: the module path's, as EvalForward.from_trainer).
-        It owns its weight pack: refresh() repacks the averaged weights and recomputes the frozen BatchNorm coefficients once per pass."""
+        It owns its weight pack: refresh() repacks the averaged weights and recomputes the frozen BatchNorm coefficients once per pass.
+        With --avg_bn_recal: the forward over the re-estimated statistics (avg_bn.BnRecal.eval_forward())."""
+        if self.bn_recal is not None:
+            return self.bn_recal.eval_forward(dtype)
         from . import infer, modules as M
         dtype = M.storage_dtype() if dtype is None else dtype
         fwd = self._forward.get(dtype)

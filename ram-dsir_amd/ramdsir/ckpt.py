@@ -161,8 +161,14 @@ def _compare_ranged(state, current, key, prefix, fields, noun, a_noun, flags):
 
 def compare_avg_weights(state, current):
     """--resume with / without --avg_weights.  current: the run's settings (avg.WeightAverage.settings()) or None when the flag is off.
-    An average cannot be made up, dropped or continued under another rule in the middle of a run."""
+    An average cannot be made up, dropped or continued under another rule in the middle of a run.  --avg_bn_recal K travels in the
+    same record (bn_recal; absent = 0, the pass off): it brings no range -- every epoch's pass uses that epoch's own batches -- but it
+    shapes <target>_val_log_avg.csv and the keep-best of the averaged model, so a file and a run that disagree about K are refused."""
     _compare_ranged(state, current, 'avg_weights', AVG_PREFIX, AVG_SETTINGS, 'averaged model', 'an averaged model', '--avg_weights')
+    saved = ((state.get('meta') or {}).get('avg_weights') or {}).get('bn_recal') or 0
+    now = (current or {}).get('bn_recal') or 0
+    if saved != now:
+        raise ValueError('--resume: the snapshot was taken with avg_weights bn_recal = %r (--avg_bn_recal), this run has %r' % (saved, now))
 
 
 def compare_grad_guard(state, current):

@@ -315,7 +315,7 @@ class Plan:
     """Buffers + launch lists for one batch geometry (N images in G groups at H x W)."""
 
     def __init__(self, bank, dtype, N, gstart, slope=0.0, training=True, options=None, fused_step=False, pad_narrow=False,
-                 side_cus=0, conv_cus=0, dgrad_cus=0, frozen_bn=False):
+                 side_cus=0, conv_cus=0, dgrad_cus=0, frozen_bn=False, recal_bn=False):
         """options: a full option set (tuning.options(...)); None: the process-wide one.  The facts of THIS plan are arguments:
         fused_step   a plan of the fused training step.  False (a module called on its own, an eval plan) never folds a BatchNorm
                      finalize and stores neither y = up2(t) nor act(bn(z)) / dz, whatever the options say
@@ -325,11 +325,23 @@ class Plan:
         dgrad_cus    >0: ... of its >= 64-channel gradient launches only (tuning.py dgrad_cus)
         frozen_bn    an inference plan (ramdsir/infer.py): BatchNorm in eval mode with coefficients that ONE rd_bn_eval_coeffs launch
                      per pass derives from the running statistics of all sites (self.bn_sites).  The forward list then holds the conv
-                     and pool launches only: no statistics (rd_conv_t.stats NULL, no rd_up_stats), no finalize, no rd_bn_apply"""
+                     and pool launches only: no statistics (rd_conv_t.stats NULL, no rd_up_stats), no finalize, no rd_bn_apply
+        recal_bn     a re-estimation plan (ramdsir/avg_bn.py): the FORWARD list of a training plan with batch statistics -- convs,
+                     pools, rd_up_stats and the explicit finalize launches, launch for launch what a module in training mode runs --
+                     whose finalize descriptors carry NULL running_mean / running_var / num_batches_tracked: every batch gets its
+                     scale / shift and the saved mean, no running statistic is touched.  ONE rd_bn_recal launch per batch folds the
+                     statistic slots of all sites (self.recal_sites) into a cumulative average.  No backward list is built"""
         if frozen_bn and (training or fused_step or len(gstart) != 2):
             raise ValueError('a frozen-BatchNorm plan is a forward-only plan with one group (training=False, fused_step=False)')
+        if recal_bn and (not training or fused_step or frozen_bn or len(gstart) != 2):
+            raise ValueError('a BatchNorm re-estimation plan is a forward-only plan with batch statistics and one group '
+                             '(training=True, fused_step=False, frozen_bn=False)')
         self.frozen_bn = bool(frozen_bn)
         self.bn_sites = []                      # frozen_bn: (gamma, beta, running_mean, running_var, scale, shift, C) per site, in launch order
+        self.recal_bn = bool(recal_bn)
+        # recal_bn: (stats pointer, conv_bias pointer or None, running_mean, running_var, num_batches_tracked, count, C, nslots, Act)
+        # per site, in launch order
+        self.recal_sites = []
         opt = T.options() if options is None else options
         self.bank, self.dtype = bank, dtype
         self.dt = L.RD_BF16 if dtype == torch.bfloat16 else L.RD_F32
@@ -551,7 +563,7 @@ class Plan:
                     else:
                         self._fwd_bn_site(node)
         self._fwd_unclaimed_finalizes()
-        if not self.training:
+        if not self.training or self.recal_bn:
             return
         # backward, reverse order; bwd_split[m] = index where module m's backward starts
         for node in reversed(self.nodes):
@@ -623,8 +635,15 @@ class Plan:
         b.conv_bias = None if o.up else self.bank.p(node.mname, node.name + '.bias').data_ptr()
         b.scale, b.shift, b.mean, b.invstd = o.scale.data_ptr(), o.shift.data_ptr(), o.mean.data_ptr(), o.invstd.data_ptr()
         self._bn_groups(o, b)
+        if self.recal_bn:
+            if kind != 'bn':
+                raise ValueError('a BatchNorm re-estimation plan needs running statistics: norm=%r has none' % kind)
+            self.recal_sites.append((b.stats, b.conv_bias, o.norm.buf(0, 'running_mean'), o.norm.buf(0, 'running_var'),
+                                     o.norm.buf(0, 'num_batches_tracked'), float(b.count[0]), o.C, self.nsl or L.STAT_SLOTS, o))
         for g in range(self.G):
             b.beta[g] = o.norm.beta_ptr(self, g, o.C)
+            if self.recal_bn:                                   # (NULL, as for InstanceNorm: rd_bn_recal owns the running statistics)
+                continue
             b.running_mean[g] = o.norm.buf_ptr(g, 'running_mean')
             b.running_var[g] = o.norm.buf_ptr(g, 'running_var')
             b.num_batches_tracked[g] = o.norm.buf_ptr(g, 'num_batches_tracked')

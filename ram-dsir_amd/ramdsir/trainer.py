@@ -31,6 +31,7 @@ class FusedTrainer:
         self._tb, self._tb_pending, self._tb_hook, self._log, self._avg, self._guard = None, None, None, None, None, None
         self._optim = None
         self._accum = None
+        self._bn_recal, self._bn_capture = None, False
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -101,12 +102,14 @@ class FusedTrainer:
         """TrainStep.arm_after_step holds ONE one-shot hook; the image grids (armed for single steps), the step log and the weight
         average (every step, once enabled) share it: one closure per step runs whichever of the three apply, in the order step log,
         averaging, image compose -- the two per-step launches of a few microseconds first, the compose and the start of its copy to
-        the host last.  All three only read the step's buffers, so the order changes no result.  Nothing is armed when none applies."""
+        the host last.  All three only read the step's buffers, so the order changes no result.  Nothing is armed when none applies.
+        A step armed with arm_bn_capture() (--avg_bn_recal) joins them with one copy of its input, behind the averaging."""
         tb, self._tb_hook = self._tb_hook, None
         log, avg = self._log, self._avg
+        cap, self._bn_capture = (self._bn_recal if self._bn_capture else None), False
         if avg is not None and self._accum is not None and not self._accum.next_is_boundary():
             avg = None                                      # rd_avg_step reads the counter, which moves at a window's last step only
-        if tb is None and log is None and avg is None:
+        if tb is None and log is None and avg is None and cap is None:
             return
 
         def hook(slot):
@@ -114,9 +117,36 @@ class FusedTrainer:
                 log.append(torch.cuda.current_stream().cuda_stream)
             if avg is not None:
                 avg.enqueue(torch.cuda.current_stream().cuda_stream)
+            if cap is not None:
+                cap.capture(slot)                           # --avg_bn_recal: the clean half of the step's input into the ring
             if tb is not None:
                 tb(slot)
         self.ts.arm_after_step(hook)
+
+    def enable_avg_bn_recal(self, K):
+        """BatchNorm re-estimation of the averaged model (ramdsir/avg_bn.py; needs enable_avg_weights first): a device ring of K
+        batches, a third set of encoder / seg-decoder BatchNorm buffers and a forward-only plan with batch statistics over the averaged
+        weights.  arm_bn_capture() makes the next step() copy the clean half of its input into the ring -- one device-to-device copy
+        behind the step through the one after-step hook, beside the step log, the averaging and the image grids; the returned
+        avg_bn.BnRecal's run_pass() re-estimates from what an epoch captured.  Only reads the trainer's buffers: training and the
+        averaged bank are bit-identical with and without it.  K == 0 constructs nothing and returns None.  Not with use_graph=True."""
+        from . import avg_bn
+        K = avg_bn.check_k(K)
+        self._refuse_graphs('enable_avg_bn_recal')
+        if K == 0:
+            return None
+        if self._avg is None:
+            raise RuntimeError('enable_avg_bn_recal: the pass re-estimates the averaged model (enable_avg_weights first)')
+        self._bn_recal = avg_bn.BnRecal(self, self._avg, K)
+        self._avg.bn_recal = self._bn_recal
+        return self._bn_recal
+
+    def arm_bn_capture(self):
+        """The next step() also copies the first B images of its input slot into the ring of enable_avg_bn_recal."""
+        self._refuse_graphs('arm_bn_capture')
+        if self._bn_recal is None:
+            raise RuntimeError('arm_bn_capture: enable_avg_bn_recal() first')
+        self._bn_capture = True
 
     def enable_avg_weights(self, mode='ema', decay=0.999, start=0):
         """From now on every step() is followed by one rd_avg_step launch (ramdsir/avg.py) that moves a second copy of the model -- the

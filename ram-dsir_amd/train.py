@@ -19,8 +19,9 @@ schedule counter, host generators, the cycled loaders' replay lists) every N epo
 continues from such a file -- bit-identically with --gpu_data or --num_workers 0 -- and --stop_after_epochs slices a run into jobs
 (ramdsir/ckpt.py); the reference can only start from a fresh initialisation; (vi) --avg_weights ema | uniform keeps a second copy of
 the model, averaged along the trajectory by one HIP launch behind every step (ramdsir/avg.py, rd_avg_step), validates it beside the live
-one where --fused_val is in use (<target>_val_log_avg.csv, model_avg_%.2f.pth) and writes final_model_avg.pth; the reference keeps the
-last iterate only; (vii) --clip_grad_norm X clips the gradient of the whole model by its global norm in front of Adam and
+one where --fused_val is in use (<target>_val_log_avg.csv, model_avg_%.2f.pth) and writes final_model_avg.pth, with
+--avg_bn_recal K after re-estimating its BatchNorm statistics from the epoch's last K batches (ramdsir/avg_bn.py, rd_bn_recal); the
+reference keeps the last iterate only; (vii) --clip_grad_norm X clips the gradient of the whole model by its global norm in front of Adam and
 --skip_nonfinite makes a step with a non-finite gradient leave no trace in the model state (parameters, moments, BatchNorm buffers),
 both decided on the device (ramdsir/guard.py: rd_grad_guard, rd_adam_step_guarded, rd_guard_sync); the reference steps on whatever
 gradient it gets (code/train.py:285-287); (viii) --weight_decay / --wd_mode / --lr_schedule / --warmup_iters / --enc_lr_mult replace the
@@ -141,8 +142,16 @@ def parse_args(argv=None):
                    help='keep a second copy of the model averaged along the training trajectory -- an exponential moving average, or the '
                         'uniform average of every iterate from --avg_start on -- by one HIP launch behind every step (ramdsir/avg.py, '
                         'rd_avg_step); with --fused_val it is validated per epoch beside the live model (<target>_val_log_avg.csv, '
-                        'model_avg_%%.2f.pth); final_model_avg.pth at the end; BatchNorm running statistics are averaged like parameters; '
-                        '--norm bn only; off by default')
+                        'model_avg_%%.2f.pth); final_model_avg.pth at the end; BatchNorm running statistics are averaged like parameters '
+                        '(see --avg_bn_recal); --norm bn only; off by default')
+    p.add_argument('--avg_bn_recal', type=int, default=0, metavar='K',
+                   help='--avg_weights: at the end of every epoch, before the averaged model is validated, and once more before '
+                        'final_model_avg.pth is written, re-estimate the BatchNorm running statistics of the averaged encoder and seg '
+                        'decoder from the last K training batches of the epoch (no new draws: the clean half of the step\'s input is '
+                        'copied into a device ring), as torch.optim.swa_utils.update_bn does with momentum=None: a forward-only HIP launch '
+                        'list with batch statistics and one rd_bn_recal launch per batch (ramdsir/avg_bn.py); num_batches_tracked = K; the '
+                        'restoration decoder takes no part in inference and keeps its averaged DSBN buffers; K at most the iterations of an '
+                        'epoch; --norm bn only; default 0 (off)')
     p.add_argument('--avg_decay', type=float, default=None, metavar='D', help='--avg_weights ema: the decay, in (0, 1); default %g' % AVG_DECAY)
     p.add_argument('--avg_start', type=int, default=None, metavar='ITER',
                    help='--avg_weights: the iteration from which on iterates are averaged; until then the averaged model is a copy of the '
@@ -481,6 +490,18 @@ def avg_settings(args):
     return args.avg_weights, AVG_DECAY if args.avg_decay is None else args.avg_decay, 0 if args.avg_start is None else args.avg_start
 
 
+def uses_bn_recal(args):
+    """--avg_bn_recal K > 0 turns the BatchNorm re-estimation of the averaged model on (ramdsir/avg_bn.py); at 0 nothing is constructed."""
+    return args.avg_bn_recal != 0
+
+
+def check_bn_recal(args, max_len):
+    """The one refusal of --avg_bn_recal that needs the length of an epoch: where it becomes known, in front of the preload, the
+    trainer and any launch."""
+    if uses_bn_recal(args) and args.avg_bn_recal > max_len:
+        raise ValueError('--avg_bn_recal %d is more than the %d iterations of an epoch of this run' % (args.avg_bn_recal, max_len))
+
+
 def uses_guard(args):
     """Either flag turns the guarded optimizer step on (ramdsir/guard.py); without both the step is the unguarded one, launch for
     launch."""
@@ -610,6 +631,12 @@ def check_args(args, world):
         raise ValueError('--avg_decay takes a decay in (0, 1), got %r' % args.avg_decay)
     if args.avg_start is not None and args.avg_start < 0:
         raise ValueError('--avg_start takes an iteration number, got %d' % args.avg_start)
+    if args.avg_bn_recal < 0:
+        raise ValueError('--avg_bn_recal takes a number of batches (0 = off), got %d' % args.avg_bn_recal)
+    if uses_bn_recal(args) and not uses_avg(args):
+        raise ValueError('--avg_bn_recal re-estimates the BatchNorm statistics of the averaged model: it needs --avg_weights')
+    if uses_bn_recal(args) and args.norm != 'bn':
+        raise ValueError('--avg_bn_recal re-estimates BatchNorm running statistics: --norm %s has none' % args.norm)
     # (the kernel receives the norm as float32: a value that is infinite there is refused with the ones that are infinite as given)
     if args.clip_grad_norm is not None and not 0.0 < args.clip_grad_norm <= float(np.finfo(np.float32).max):      # NaN fails both
         raise ValueError('--clip_grad_norm takes a positive finite norm, got %r' % args.clip_grad_norm)
@@ -885,10 +912,16 @@ def open_state(args, trainer, fingerprint_args, resume_state):
     return state_io
 
 
-def train_epoch(args, trainer, loaders, resident, log, iter_num):
+def train_epoch(args, trainer, loaders, resident, log, iter_num, recal=None, epoch_len=0):
     """One pass over the zipped loaders; returns iter_num behind it.  One batch of look-ahead: the step of batch i also mixes batch
     i+1 (RAM) in its tail, beside Adam and the weight repack (FusedTrainer.step next_batch; the last iteration of an epoch -- or of
-    --max_iters -- has no successor and runs the classical step)."""
+    --max_iters -- has no successor and runs the classical step).
+    recal (--avg_bn_recal): the last K of the epoch's epoch_len iterations (fewer where --max_iters ends it early) also copy their
+    input into the ring."""
+    if recal is not None:
+        recal.begin_epoch()
+        n_epoch = min(epoch_len, args.max_iters - iter_num) if args.max_iters else epoch_len
+        first_captured = iter_num + max(0, n_epoch - recal.K)
     def on_device(batches):
         if resident is not None:                        # --gpu_data: one rd_fundus_batch / rd_prostate_batch launch
             return resident.on_device(batches)
@@ -904,6 +937,8 @@ def train_epoch(args, trainer, loaders, resident, log, iter_num):
         log_images = log.rank0 and args.tb_images > 0 and iter_num % args.tb_images == 0      # train.py:306, 475
         if log_images:
             trainer.arm_tb_images()                     # this step also composes the grids of its batch and starts their copy
+        if recal is not None and iter_num >= first_captured:
+            trainer.arm_bn_capture()                    # ... and this one leaves the clean half of its input in the ring
         trainer.step(*cur, next_batch=nxt)
         cur = nxt
         log.after_step(iter_num, log_images)
@@ -935,6 +970,7 @@ def main(args):
     raw, samplers, loaders, max_len = make_loaders(args, data_root, world, rank, bsl, domain_idx_list, replay=uses_ckpt(args))
     if uses_accum(args):
         accum_totals(args, max_len)                                  # a run with no complete window is refused here
+    check_bn_recal(args, max_len)                                    # ... and a K beyond the epoch here
     resident = None
     if args.gpu_data:
         # decode once, keep the pixels on this GPU (ramdsir/gpu_data.py); the loaders above only draw
@@ -949,6 +985,11 @@ def main(args):
     modules, trainer, (H, W), total_iters = build_trainer(args, rank, raw, resident, bsl, max_len)
     # --avg_weights: the second bank, a copy of the initial model (rank-local under data parallelism, as the BatchNorm buffers are)
     avg = trainer.enable_avg_weights(*avg_settings(args)) if uses_avg(args) else None
+    # --avg_bn_recal: the ring, the third set of BatchNorm buffers and the forward-only plan over the averaged weights (rank-local too)
+    recal = trainer.enable_avg_bn_recal(args.avg_bn_recal) if uses_bn_recal(args) else None
+    if recal is not None and rank == 0:
+        print('avg_bn_recal: the last %d batches of an epoch in a ring of %.1f MB; %d BatchNorm sites re-estimated per pass'
+              % (recal.K, recal.ring.buf.numel() * recal.ring.buf.element_size() / 1e6, recal.forward.n_sites))
     # --clip_grad_norm / --skip_nonfinite: the guarded tail replaces Adam + repack in the step; the shadows copy the initial buffers
     guard = trainer.enable_grad_guard(guard_max_norm(args)) if uses_guard(args) else None
     # the five optimizer flags: the grouped Adam replaces rd_adam_step in the step (under the guard's state word where both are on)
@@ -982,10 +1023,14 @@ def main(args):
         for sp in samplers:
             if sp is not None:
                 sp.set_epoch(epoch)
-        iter_num = train_epoch(args, trainer, loaders, resident, log, iter_num)
+        iter_num = train_epoch(args, trainer, loaders, resident, log, iter_num, recal, max_len)
         log.throughput(iter_num)
         torch.cuda.synchronize()
         t_train = time.time() - t_epoch
+        if recal is not None:
+            # the statistics of the averaged weights from this epoch's last batches, in front of everything that reads them below
+            # (the _avg validation, model_avg_%.2f.pth) and, behind the last epoch, final_model_avg.pth
+            recal.run_pass()
         # validation on the held-out domain + keep-best checkpoint rotation (train.py:331-350)
         avg_dice = val(modules[0], modules[1], epoch) if val is not None else None
         if world > 1:
@@ -1037,6 +1082,8 @@ def main(args):
     elif rank == 0:
         save_checkpoint(os.path.join(args.save_path, 'final_model.pth'), *modules)
         if avg is not None:
+            if recal is not None:
+                recal.run_pass()                            # once more, over the last epoch's batches: the same bits
             torch.save(dict(avg.state_dicts()), os.path.join(args.save_path, 'final_model_avg.pth'))
         print('\nSave Final Model to {}'.format(args.save_path))
     log.close()
