@@ -40,10 +40,11 @@ def slot_sums_model(slots, nslots=L.STAT_SLOTS):
     return s1, s2
 
 
-def fwd_stat_model(s1, s2, count, conv_bias=None):
+def fwd_stat_model(s1, s2, count, conv_bias=None, with_var=False):
     """csrc/bn_fin.h fwd_stat, operation by operation (contraction off): (mean, unb) float32 [C].
     m0 = s1 / count; var = max(s2 / count - m0 * m0, 0) in float64; mean = float32(m0 + conv_bias);
-    unb = float32(var * count / (count - 1)) for count > 1, float32(var) otherwise.  count is the float32 the kernel receives."""
+    unb = float32(var * count / (count - 1)) for count > 1, float32(var) otherwise.  count is the float32 the kernel receives.
+    with_var: (mean, unb, float32(var)) -- the biased variance that invstd is taken from (tests/bn_fin_model.py)."""
     f32, f64 = np.float32, np.float64
     s1, s2 = np.asarray(s1, f64), np.asarray(s2, f64)
     cnt = f64(f32(count))
@@ -55,7 +56,8 @@ def fwd_stat_model(s1, s2, count, conv_bias=None):
         vard = np.where(vard < 0.0, 0.0, vard)
         mean = (m0 + cb.astype(f64)).astype(f32)
         unb = ((vard * cnt) / (cnt - 1.0)).astype(f32) if cnt > 1.0 else vard.astype(f32)
-    return mean, unb
+        var = vard.astype(f32)
+    return (mean, unb, var) if with_var else (mean, unb)
 
 
 def update_model(run, x, k):

@@ -22,9 +22,21 @@ def _dev_copy(keep, desc):
     return C.addressof(desc)
 
 
+T6 = [0, 1, 1, 2, 0, 3, 0, 1]          # G = FIN_MAX_G groups on four BatchNorms: two chains of three, interleaved (bn_fin_model.TOPOLOGIES)
+
+
+def _modmap(shared, G):
+    """The module index of every group: True = one BatchNorm shared by all, False = one per group (DSBN), or the map itself."""
+    if isinstance(shared, (list, tuple)):
+        assert len(shared) == G
+        return list(shared)
+    return [0] * G if shared else list(range(G))
+
+
 def _bn_state(keep, G, Cc, shared, gen):
-    """Parameters and buffers of the BatchNorm(s) behind G groups: one shared module, or one per group (DSBN)."""
-    nmod = 1 if shared else G
+    """Parameters and buffers of the BatchNorm(s) behind G groups, by module map (_modmap)."""
+    mod = _modmap(shared, G)
+    nmod = max(mod) + 1
     st = dict(gamma=[keep(U.fdev(1.0 + 0.2 * torch.randn(Cc, generator=gen))) for _ in range(nmod)],
               beta=[keep(U.fdev(0.3 * torch.randn(Cc, generator=gen))) for _ in range(nmod)],
               rm=[keep(U.fdev(0.1 * torch.randn(Cc, generator=gen))) for _ in range(nmod)],
@@ -32,7 +44,7 @@ def _bn_state(keep, G, Cc, shared, gen):
               nbt=[keep(torch.full((), 3, dtype=torch.long, device=U.dev())) for _ in range(nmod)],
               dgamma=[keep(U.fdev(0.05 * torch.randn(Cc, generator=gen))) for _ in range(nmod)],
               dbeta=[keep(U.fdev(0.05 * torch.randn(Cc, generator=gen))) for _ in range(nmod)])
-    st['mod'] = [0] * G if shared else list(range(G))
+    st['mod'] = mod
     return st
 
 
@@ -77,6 +89,7 @@ FWD_ROUTES = [
     # name, dtype, taps, Cin, Cout, N, H, W, gstart, shared BatchNorm
     ('small_fwd_32_32', 'bf16', 9, 32, 32, 4, 70, 100, [0, 2, 4], True),            # conv_small_fwd_kernel, several tiles per workgroup
     ('small_fwd_16_16_dsbn', 'bf16', 9, 16, 16, 3, 33, 65, [0, 1, 2, 3], False),
+    ('small_fwd_16_16_t6', 'bf16', 9, 16, 16, 9, 33, 65, [0, 1, 2, 3, 5, 6, 7, 8, 9], T6),      # the LDS-delivery prologue, chains of three
     ('small_k1_32_16', 'bf16', 1, 32, 16, 4, 20, 20, [0, 2, 4], True),              # conv_small_kernel (1x1)
     ('ws_64_64', 'bf16', 9, 64, 64, 8, 103, 95, [0, 3, 8], True),                   # conv_ws_kernel (persistent, >= 300 workgroups)
     ('pp_256_256', 'bf16', 9, 256, 256, 4, 25, 25, [0, 2, 4], True),                # few tiles: conv_pp_kernel / conv_pf_kernel
@@ -136,7 +149,8 @@ def test_forward_finalize_folded_into_the_consuming_conv(case):
             for k in ('rm', 'rv', 'nbt'):
                 for a, b in zip(st[k], ref['st'][k]):
                     assert torch.equal(a, b), k
-            assert int(st['nbt'][0]) == 3 + (G if shared else 1)
+            for m, t in enumerate(st['nbt']):
+                assert int(t) == 3 + st['mod'].count(m)
         else:                                              # a non-owner leaves what happens once per BatchNorm call alone
             for k in ('rm', 'rv', 'nbt'):
                 for a, b in zip(st[k], snap[k]):
@@ -218,6 +232,7 @@ BWD_ROUTES = [
     # name, dtype, Cz (channels of dz = the conv's Cout), Ca (the conv's Cin), N, H, W, gstart, shared
     ('fused_32_32', 'bf16', 32, 32, 4, 70, 100, [0, 2, 4], True),                   # conv_small_bwd_fused_kernel / conv_small_kernel
     ('small_16_16_dsbn', 'bf16', 16, 16, 3, 33, 65, [0, 1, 2, 3], False),
+    ('small_16_16_t6', 'bf16', 16, 16, 9, 33, 65, [0, 1, 2, 3, 5, 6, 7, 8, 9], T6),      # ... and bwd_pair of its weight gradient
     ('ws2_64_64', 'bf16', 64, 64, 7, 100, 104, [0, 2, 7], True),                    # conv_ws_kernel<2, *, true>
     ('pf_128_128', 'bf16', 128, 128, 4, 25, 25, [0, 2, 4], True),
     ('f32_16_16', 'f32', 16, 16, 4, 16, 32, [0, 1, 4], True),
