@@ -787,7 +787,8 @@ int64_t rd_step_log_workspace(int64_t n);
  * range, of which only these two words are ever written -- same-address atomics are served one after the other, so the pairs of
  * different ranges sit in different lines; sums_dev holds n * S words)
  * each workgroup reduces its part and issues one pair of 64-bit integer atomic adds: integer addition commutes, so the sums are the
- * same bits on every run; no floating point.  Work decomposition: range i is cut into chunks of RD_SNAP_CHUNK bytes from its start
+ * same bits on every run; no floating point.  Work decomposition (csrc/range_walk.h: the ONE text of this walk, which rd_avg_step,
+ * rd_guard_sync and rd_optim_step share): range i is cut into chunks of RD_SNAP_CHUNK bytes from its start
  * (the last one ragged), chunk0 = the number of chunks of the ranges in front of it; the grid is flat over the total_chunks chunks and
  * a workgroup finds its range by binary search over chunk0 in table_dev -- the SAME n entries in device memory, uploaded once by the
  * caller, as rd_pack_weights_batched's table_dev.  table_host is read for validation only; nothing on the device is dereferenced by
@@ -823,12 +824,10 @@ int rd_snapshot(const rd_snap_range_t* table_host, const rd_snap_range_t* table_
  *                                                                     denormals kept), never an fma;
  *                              w = one_minus_decay (mode 0, exponential moving average) or 1.0f / (float)(k + 1) (mode 1, the uniform
  *                              average of the iterates start + 1, ..., s), the division correctly rounded
- * -- numpy float32 reproduces it bit for bit (ramdsir/avg.py model()).  Work decomposition, as rd_snapshot's: range i is cut into
- * chunks of RD_AVG_CHUNK bytes from its start (the last one ragged), chunk0 = the number of chunks of the ranges in front of it; the grid
- * is flat over the total_chunks chunks and a workgroup finds its range by binary search over chunk0 in table_dev -- the SAME n entries
- * in device memory, uploaded once by the caller.  table_host is read for validation only; nothing on the device is dereferenced by
- * the host.  Within a chunk the part where src and dst are both 16-byte aligned moves with 16-byte loads and stores, the words in
- * front of and behind it (or the whole chunk, when the two sides are aligned differently) with 4-byte accesses.
+ * -- numpy float32 reproduces it bit for bit (ramdsir/avg.py model()).  Work decomposition: the walk of csrc/range_walk.h as
+ * described for rd_snapshot above, over chunks of RD_AVG_CHUNK bytes -- chunk0, total_chunks, table_dev (the SAME n entries in
+ * device memory, uploaded once by the caller), table_host (read for validation only; nothing on the device is dereferenced by the
+ * host) and the 16-byte / 4-byte split of a chunk between src and dst mean what they mean there.
  * Exactly ONE launch on `stream`, through the library's one launch site (none for n == 0 or when every range is empty, which
  * succeed).  No hipMemcpyAsync / hipMemsetAsync; allocates nothing, synchronises nothing; the caller owns every buffer.  Returns,
  * before anything is launched: -1 n < 0 (or > 2^24), a null iter_dev, or (n > 0) a null table; -2 a byte count that is negative or not
@@ -913,8 +912,8 @@ int rd_bn_recal(const rd_bn_recal_site_t* sites_host, const rd_bn_recal_site_t* 
  *
  * rd_guard_sync: ONE launch over n range pairs {live, shadow, bytes, chunk0}: with guard->skip set, live <- shadow (the BatchNorm
  * buffers the forward pass of the skipped step has moved are rolled back); otherwise shadow <- live (the last good step is
- * remembered).  A byte copy: int64 ranges and NaN bit patterns pass through untouched.  Work decomposition and validation codes are
- * rd_avg_step's, with RD_GUARD_CHUNK for RD_AVG_CHUNK: -1 n < 0 (or > 2^24), a null guard_dev, or (n > 0) a null table; -2 a byte
+ * remembered).  A byte copy: int64 ranges and NaN bit patterns pass through untouched.  Work decomposition (csrc/range_walk.h) and
+ * validation codes are rd_avg_step's, with RD_GUARD_CHUNK for RD_AVG_CHUNK: -1 n < 0 (or > 2^24), a null guard_dev, or (n > 0) a null table; -2 a byte
  * count that is negative or not a multiple of 4; -3 a misaligned live / shadow / guard_dev (or a null live / shadow with bytes > 0);
  * -5 a chunk0 column or total_chunks that does not match the byte counts.  The live and shadow ranges must not overlap (not checked).
  * None of the three allocates, synchronises or copies anything; every launch goes through the library's one launch site. */
@@ -957,12 +956,11 @@ int rd_guard_sync(const rd_guard_range_t* table_host, const rd_guard_range_t* ta
  * text of the per-element arithmetic (csrc/adam_body.h).
  *
  * The table: n_ranges <= 4096 entries {first, count, lr_mult, weight_decay, chunk0}, sorted, contiguous, covering [0, n) exactly,
- * count >= 1.  Range starts have any 4-byte alignment (the arena packs tensors back to back).  Work decomposition: rd_avg_step's --
- * range i is cut into chunks of RD_OPT_CHUNK ELEMENTS from its start (the last one ragged, a chunk never straddles two ranges),
- * chunk0 = the number of chunks of the ranges in front of it, the grid is flat over all chunks (not capped), a workgroup finds its
- * range by a search over the chunk0 column of the device table (one load per thread and a count over the workgroup, behind binary
- * steps only above 256 ranges) -- per workgroup, never per element -- and moves the part of its
- * chunk that starts at a 16-byte boundary of all four arenas with 16-byte accesses, the words in front of and behind it one by one.
+ * count >= 1.  Range starts have any 4-byte alignment (the arena packs tensors back to back).  Work decomposition: the walk of
+ * csrc/range_walk.h (see rd_snapshot) over chunks of RD_OPT_CHUNK ELEMENTS, the grid flat over all chunks (not capped), with a
+ * lookup of its own: a workgroup finds its range by a search over the chunk0 column of the device table (one load per thread and a
+ * count over the workgroup, behind binary steps only above 256 ranges) -- per workgroup, never per element -- and moves the part of
+ * its chunk that starts at a 16-byte boundary of all four arenas with 16-byte accesses, the words in front of and behind it one by one.
  *
  * Two launches.  (1) prepare, one thread, all in fp64, each word rounded once to fp32: with it = *iter,
  *     s(it) = schedule 0 (poly):     it == 0 ? 1 : (1 - (it - 1) / total_iters) ^ 0.9      rd_adam_step's expression, the reference's

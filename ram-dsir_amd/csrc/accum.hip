@@ -16,10 +16,11 @@
 // of rd_adam_step and not the chunk table of avg.hip / optim.hip (profiles/optim.md: what the table costs on a single arena).  The
 // part of the arena behind grad's first 16-byte boundary moves as 16-byte accesses where acc shares that phase -- ACC_BATCH quads of
 // each side per thread and trip, every load issued before the first store -- the words in front of and behind it (at most six) one
-// by one; arenas that are aligned differently have no common boundary and go word by word throughout, in the same batched form.
+// by one; arenas that are aligned differently have no common boundary and go word by word throughout, in the same batched form
+// (the alignment split of range_walk.h, over 64-bit indices).
 #include <cstring>
 
-#include "common.h"
+#include "range_walk.h"
 #include "../../include/ramdsir.h"
 
 namespace {
@@ -30,10 +31,7 @@ constexpr int ACC_BATCH = 4;                                        // accesses 
 // trainer's arena (a few million words) still takes ONE trip of the loop -- 4 Mi words on the 16-byte path
 constexpr int ACC_MAX_BLOCKS = 1024;
 
-// the arenas are device allocations: global, not generic, loads and stores
-typedef __attribute__((address_space(1))) unsigned g_u32;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+using namespace rdwalk;
 
 // MODE: 0 copy, 1 add, 2 mean.  g the gradient word, a the accumulated one
 template <int MODE>
@@ -50,12 +48,8 @@ __global__ __launch_bounds__(ACC_THREADS) void grad_accum_kernel(unsigned* grad_
     g_u32* dst = MODE == 2 ? grad : acc;
     const long long tid = (long long)blockIdx.x * ACC_THREADS + threadIdx.x;
     const long long nthreads = (long long)gridDim.x * ACC_THREADS;
-    // [0, head) word by word up to grad's first 16-byte boundary, then nq whole quads, then [tail, n) word by word; sides that are
-    // aligned differently have no common boundary: head = n
-    long long head = (long long)((0 - ((uintptr_t)grad_ >> 2)) & 3);
-    if ((((uintptr_t)grad_ ^ (uintptr_t)acc_) & 15) != 0) head = n;
-    head = head < n ? head : n;
-    const long long nq = (n - head) >> 2, tail = head + 4 * nq;
+    const Split<long long> sp = split16(n, grad_, acc_);
+    const long long head = sp.head, nq = sp.nq, tail = sp.tail;
     const g_u32x4* g4 = (const g_u32x4*)(grad + head);
     const g_u32x4* a4 = (const g_u32x4*)(acc + head);
     g_u32x4* d4 = (g_u32x4*)(dst + head);

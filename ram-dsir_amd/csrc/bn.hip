@@ -43,8 +43,8 @@ __global__ __launch_bounds__(64 * RD_MAX_GROUPS) void bn_finalize_fwd_kernel(con
     }
     float mean, invstd, unb = 0.f;
     if (p.training) {
-        s1 = wave_sum_d(s1);
-        s2 = wave_sum_d(s2);
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
         const rdfin::FwdStat r = rdfin::fwd_stat(s1, s2, p.count[g], cbias, p.eps);     // shared with the folded finalize (bn_fin.h)
         mean = r.mean;
         invstd = r.invstd;
@@ -102,8 +102,8 @@ __global__ __launch_bounds__(64 * RD_MAX_GROUPS) void bn_finalize_bwd_kernel(con
         sgzd += p.bstats[((size_t)(g * RD_STAT_SLOTS + k) * p.C + c) * 2 + 1];
     }
     const float mu = p.mean[g * p.C + c], is = p.invstd[g * p.C + c], gam = p.gamma[g][c];
-    s1d = wave_sum_d(s1d);
-    sgzd = wave_sum_d(sgzd);
+    s1d = wave_sum(s1d);
+    sgzd = wave_sum(sgzd);
     if (lane == 0) {
         const rdfin::BwdStat r = rdfin::bwd_stat(s1d, sgzd, mu, is);                     // shared with the folded finalize (bn_fin.h)
         float P, Q, R;
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(64 * RD_MAX_GROUPS) void bn_finalize_bwd_kernel(con
 // (nn.InstanceNorm2d = BatchNorm statistics per (image, channel) without affine or running statistics: the BatchNorm kernels with one
 // group per image, gamma = 1, beta = 0 and null running-statistics pointers.)
 __device__ __forceinline__ double block_sum_d(double v, double* s_tmp) {
-    v = wave_sum_d(v);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) s_tmp[threadIdx.x >> 6] = v;
     __syncthreads();

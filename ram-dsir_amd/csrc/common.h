@@ -112,17 +112,25 @@ __device__ __forceinline__ void up2_coord(int d, int n_src, int& i0, int& i1, fl
     lam = s - (float)i0;
 }
 
-// block-wide sum of one float per thread (blockDim.x multiple of 64, <= 1024); result valid in thread 0
-__device__ __forceinline__ float wave_sum(float v) {
+// sum over the 64 lanes of a wave in the fixed xor tree (offsets 32, 16, ..., 1): every lane ends with the same bits
+template <typename T>
+__device__ __forceinline__ T wave_xor_tree(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ float wave_sum(float v) { return wave_xor_tree(v); }
+__device__ __forceinline__ double wave_sum(double v) { return wave_xor_tree(v); }
+__device__ __forceinline__ long long wave_sum(long long v) { return wave_xor_tree(v); }
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) { return wave_xor_tree(v); }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+// the gradient-health sum (rd_step_log, rd_grad_guard): s += x * x for a finite x (the product of two converted floats is exact in
+// fp64); a NaN or an infinity is counted instead
+__device__ __forceinline__ void accumulate(float x, double& s, int& bad) {
+    const bool finite = (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;
+    const double d = finite ? (double)x : 0.0;
+    s = d * d + s;
+    bad += finite ? 0 : 1;
 }
 
 // Dispatch overrides (experiments, the forced-dispatch tests) exist only in the DEBUG build of the library

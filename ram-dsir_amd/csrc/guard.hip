@@ -8,16 +8,16 @@
 // second launch and read by rd_adam_step_guarded and rd_guard_sync through the same device pointer; every launch argument is the
 // same at every step, and the host reads the state only where it synchronises anyway.
 //
-// rd_grad_guard is the health pass of rd_step_log (csrc/step_log.hip; its accumulate / wave_sum helpers are restated here) over ONE
+// rd_grad_guard is the health pass of rd_step_log (csrc/step_log.hip; accumulate and wave_sum are common.h's for both) over ONE
 // group: (1) one workgroup per chunk of RD_LOG_CHUNK gradient elements sums g * g in fp64 over its finite elements and counts the
 // others -> partial[chunk]; (2) one wave adds the partials (lane l takes l, l + 64, ... in ascending order, then the fixed xor tree
 // over the lanes) and writes norm, scale, skip and the counters.  Every order is fixed by the indices: no atomics, the same bits on
 // every run.
 //
-// rd_guard_sync is ONE launch over range pairs {live, shadow} in rd_avg_step's work decomposition (csrc/avg.hip, restated): a flat
-// grid over chunks of RD_GUARD_CHUNK bytes, binary search over the chunk0 column, 16-byte moves where both sides are aligned, words
-// otherwise.  skip set: live <- shadow (roll the BatchNorm buffers back); otherwise shadow <- live (remember the last good step).
-#include "common.h"
+// rd_guard_sync is ONE launch over range pairs {live, shadow} in the walk of range_walk.h over chunks of RD_GUARD_CHUNK bytes: its
+// lookup, its batched copy of a chunk, its host-side table check.  skip set: live <- shadow (roll the BatchNorm buffers back);
+// otherwise shadow <- live (remember the last good step).
+#include "range_walk.h"
 #include "../../include/ramdsir.h"
 
 namespace {
@@ -33,25 +33,6 @@ struct GuardPartial {
     double sum;
     long long count;
 };
-
-// s += x * x for a finite x (the product of two converted floats is exact in fp64); a NaN or an infinity is counted instead
-__device__ __forceinline__ void accumulate(float x, double& s, int& bad) {
-    const bool finite = (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;
-    const double d = finite ? (double)x : 0.0;
-    s = d * d + s;
-    bad += finite ? 0 : 1;
-}
-
-__device__ __forceinline__ double lanes_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long lanes_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // grid (chunks of the arena): partial[chunk] = {sum of squares of the finite elements, number of the others}
 __global__ __launch_bounds__(GG_THREADS) void grad_guard_partial_kernel(const float* __restrict__ grad, long long n,
@@ -87,8 +68,8 @@ __global__ __launch_bounds__(GG_THREADS) void grad_guard_partial_kernel(const fl
     accumulate(e, s, bad);
     __shared__ double s_sum[GG_THREADS / 64];
     __shared__ long long s_bad[GG_THREADS / 64];
-    s = lanes_sum(s);
-    const long long m = lanes_sum((long long)bad);
+    s = wave_sum(s);
+    const long long m = wave_sum((long long)bad);
     if ((t & 63) == 0) { s_sum[t >> 6] = s; s_bad[t >> 6] = m; }
     __syncthreads();
     if (t == 0) {
@@ -120,8 +101,8 @@ __global__ __launch_bounds__(64) void grad_guard_final_kernel(const GuardPartial
             bad += r[k].count;
         }
     }
-    s = lanes_sum(s);
-    bad = lanes_sum(bad);
+    s = wave_sum(s);
+    bad = wave_sum(bad);
     if (lane != 0) return;
     const float norm = (float)sqrt(s);
     const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
@@ -144,50 +125,17 @@ constexpr int GS_QUADS = RD_GUARD_CHUNK / 16 / GS_THREADS;          // 16-byte a
 static_assert(RD_GUARD_CHUNK % (GS_THREADS * 16) == 0 && GS_QUADS >= 1 && GS_QUADS <= 8, "a chunk is one batch of whole quads");
 static_assert(sizeof(rd_guard_range_t) == 32, "rd_guard_range_t is four 8-byte words");
 
-// the ranges are device allocations: global, not generic, loads and stores
-typedef __attribute__((address_space(1))) unsigned g_u32;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-
 __global__ __launch_bounds__(GS_THREADS) void guard_sync_kernel(const rd_guard_range_t* __restrict__ table, int n,
                                                                 const rd_guard_state_t* __restrict__ guard) {
     const long long c = blockIdx.x;
-    const int t = threadIdx.x;
-    // the last range whose first chunk is <= c: an empty range shares its first chunk with the range behind it and is never chosen
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].chunk0 <= c) lo = mid; else hi = mid - 1;
-    }
-    const rd_guard_range_t r = table[lo];
-    const long long w0 = (c - r.chunk0) * GS_WORDS;                 // first word of this chunk within its range
-    const long long rest = (r.bytes >> 2) - w0;
-    if (c < r.chunk0 || rest <= 0) return;                          // a table that does not match the grid: touch nothing
-    const int len = rest < GS_WORDS ? (int)rest : GS_WORDS;
+    const rd_guard_range_t r = table[rdwalk::find_range(table, n, c)];
+    long long w0;                                                   // first word of this chunk within its range
+    const int len = rdwalk::chunk_len<GS_WORDS>(c, r.chunk0, r.bytes >> 2, w0);
+    if (len == 0) return;
     const bool back = guard->skip != 0;                             // uniform over the grid: live <- shadow
-    const g_u32* __restrict__ src = (const g_u32*)((const unsigned*)(back ? r.shadow : r.live) + w0);
-    g_u32* dst = (g_u32*)((unsigned*)(back ? r.live : r.shadow) + w0);
-    // [0, head) word by word up to the first 16-byte boundary, then nq whole quads, then [tail, len) word by word; sides that are
-    // aligned differently have no common boundary: head = len
-    int head = (int)((0 - ((uintptr_t)src >> 2)) & 3);
-    if ((((uintptr_t)src ^ (uintptr_t)dst) & 15) != 0) head = len;
-    head = head < len ? head : len;
-    const int nq = (len - head) >> 2, tail = head + 4 * nq;
-    const g_u32x4* __restrict__ s4 = (const g_u32x4*)(src + head);
-    g_u32x4* d4 = (g_u32x4*)(dst + head);
-    u32x4 p[GS_QUADS];
-#pragma unroll
-    for (int j = 0; j < GS_QUADS; ++j) {
-        const int q = t + j * GS_THREADS;
-        if (q < nq) p[j] = s4[q];
-    }
-#pragma unroll
-    for (int j = 0; j < GS_QUADS; ++j) {
-        const int q = t + j * GS_THREADS;
-        if (q < nq) d4[q] = p[j];
-    }
-    for (int i = t; i < head; i += GS_THREADS) dst[i] = src[i];
-    for (int i = tail + t; i < len; i += GS_THREADS) dst[i] = src[i];
+    const rdwalk::g_u32* src = (const rdwalk::g_u32*)((const unsigned*)(back ? r.shadow : r.live) + w0);
+    rdwalk::g_u32* dst = (rdwalk::g_u32*)((unsigned*)(back ? r.live : r.shadow) + w0);
+    rdwalk::copy_chunk<GS_QUADS, GS_THREADS>(src, dst, len);
 }
 
 }  // namespace
@@ -214,17 +162,12 @@ extern "C" int rd_guard_sync(const rd_guard_range_t* table_host, const rd_guard_
     if (n == 0) return 0;
     if (!table_host || !table_dev) return -1;
     if ((uintptr_t)guard_dev % 8 != 0) return -3;
-    int64_t chunks = 0;
-    for (int i = 0; i < n; ++i) {
-        const rd_guard_range_t& r = table_host[i];
+    const int64_t chunks = rdwalk::walk_table<RD_GUARD_CHUNK>(table_host, n, total_chunks, [](const rd_guard_range_t& r) -> int64_t {
         if (r.bytes < 0 || r.bytes % 4 != 0) return -2;
         if ((uintptr_t)r.live % 4 != 0 || (uintptr_t)r.shadow % 4 != 0 || (r.bytes > 0 && (!r.live || !r.shadow))) return -3;
-        if (r.chunk0 != chunks) return -5;
-        chunks += (r.bytes + RD_GUARD_CHUNK - 1) / RD_GUARD_CHUNK;
-        if (chunks > 0x7fffffffll) return -5;
-    }
-    if (chunks != total_chunks) return -5;
-    if (chunks == 0) return 0;                                      // every range is empty: nothing to launch
+        return r.bytes;
+    });
+    if (chunks <= 0) return (int)chunks;                            // a code; or every range is empty: nothing to launch
     rd_launch(guard_sync_kernel, dim3((unsigned)chunks), dim3(GS_THREADS), 0, (hipStream_t)stream, table_dev, n, guard_dev);
     return (int)hipGetLastError();
 }

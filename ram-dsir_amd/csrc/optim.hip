@@ -5,11 +5,10 @@
 // csrc/loss.hip: no decay, lr / 2 on the encoder, poly) is the two-range special case, and with that table the bits are the same:
 // the per-element arithmetic is the ONE text of adam_body.h.
 //
-// TWO launches.  The prepare launch is one thread in fp64.  The update launch uses rd_avg_step's decomposition (csrc/avg.hip),
-// restated for elements: range i is cut into chunks of RD_OPT_CHUNK elements from its start (the last one ragged, a chunk never
-// straddles two ranges), chunk0 is the number of chunks of the ranges in front of it, the grid is flat over the chunks of all ranges
-// (one workgroup per chunk, not capped: an arena of 2^31 chunks would be 2^43 elements), and a workgroup finds its range by a
-// search over the chunk0 column -- once per workgroup, its threads looking at one entry each.  Multiplier, decay and decay mode are
+// TWO launches.  The prepare launch is one thread in fp64.  The update launch is the walk of range_walk.h over chunks of
+// RD_OPT_CHUNK ELEMENTS (its alignment split and host-side table check; one workgroup per chunk, not capped: an arena of 2^31
+// chunks would be 2^43 elements), with a lookup of its own, which also checks the arena bounds: a workgroup finds its range by a
+// search over the chunk0 column once per workgroup, its threads looking at one entry each.  Multiplier, decay and decay mode are
 // therefore uniform over the workgroup: the decay variant is chosen by ONE scalar branch into a chunk body compiled for it, and a range without decay executes neither decay
 // operation (not a multiplication by one: -0 and NaN payloads would pass, but the text would no longer be rd_adam_step's).
 // Range starts have any 4-byte alignment (the arena packs tensors back to back): the part of a chunk behind the first 16-byte
@@ -17,7 +16,7 @@
 // of and behind it one by one; arenas that are aligned differently from one another have no common boundary and go word by word.
 #include <cmath>
 
-#include "common.h"
+#include "range_walk.h"
 #include "adam_body.h"
 #include "../../include/ramdsir.h"
 
@@ -54,7 +53,8 @@ __device__ __forceinline__ void optim_element(float& w, float& m, float& v, floa
 template <bool GUARDED, int WD>
 __device__ __forceinline__ void optim_chunk(g_f32* w, const g_f32* __restrict__ g, g_f32* m, g_f32* v, int len, int head, const OptConsts& k) {
     const int t = threadIdx.x;
-    const int nq = (len - head) >> 2, tail = head + 4 * nq;
+    const rdwalk::Split<int> sp = rdwalk::split_at(len, head);
+    const int nq = sp.nq, tail = sp.tail;
     g_f32x4* w4 = (g_f32x4*)(w + head);
     const g_f32x4* __restrict__ g4 = (const g_f32x4*)(g + head);
     g_f32x4* m4 = (g_f32x4*)(m + head);
@@ -162,9 +162,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_update_kernel(const rd_opti
     const g_f32* g = (const g_f32*)(p.grad + base);
     g_f32* m = (g_f32*)(p.exp_avg + base);
     g_f32* v = (g_f32*)(p.exp_avg_sq + base);
-    int head = (int)((0 - ((uintptr_t)w >> 2)) & 3);
-    if (((((uintptr_t)w ^ (uintptr_t)g) | ((uintptr_t)w ^ (uintptr_t)m) | ((uintptr_t)w ^ (uintptr_t)v)) & 15) != 0) head = len;
-    head = head < len ? head : len;
+    const int head = rdwalk::split_head(len, w, g, m, v);
     if (!(r.weight_decay > 0.f)) {
         optim_chunk<GUARDED, 0>(w, g, m, v, len, head, k);
     } else if (p.wd_mode == 0) {
@@ -183,18 +181,16 @@ extern "C" int rd_optim_step(const rd_optim_t* p, const rd_optim_range_t* table_
     if (!p->param || !p->grad || !p->exp_avg || !p->exp_avg_sq || !p->iter || !p->hyper_out || p->n < 1) return -1;
     if (p->schedule < 0 || p->schedule > 2 || (p->wd_mode != 0 && p->wd_mode != 1)) return -4;
     if (p->warmup_iters < 0 || p->warmup_iters >= p->total_iters) return -4;
-    int64_t next = 0, chunks = 0;
-    for (int i = 0; i < n_ranges; ++i) {
-        const rd_optim_range_t& r = table_host[i];
+    int64_t next = 0;
+    auto size_of = [&](const rd_optim_range_t& r) -> int64_t {
         if (r.count < 1 || r.first != next || r.count > p->n - next) return -2;
         if (!std::isfinite(r.lr_mult) || !(r.lr_mult > 0.f)) return -3;
         if (!std::isfinite(r.weight_decay) || r.weight_decay < 0.f) return -3;
-        if (r.chunk0 != chunks) return -5;
         next += r.count;
-        chunks += (r.count + RD_OPT_CHUNK - 1) / RD_OPT_CHUNK;
-    }
-    if (next != p->n) return -2;
-    if (chunks != total_chunks || chunks > 0x7fffffffll) return -5;
+        return r.count;
+    };
+    const int64_t chunks = rdwalk::walk_table<RD_OPT_CHUNK, false>(table_host, n_ranges, total_chunks, size_of, [&] { return next != p->n ? -2 : 0; });
+    if (chunks < 0) return (int)chunks;
     hipStream_t st = (hipStream_t)stream;
     rd_launch(optim_prepare_kernel, dim3(1), dim3(1), 0, st, *p, guard_dev);
     if (guard_dev)

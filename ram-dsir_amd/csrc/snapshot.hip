@@ -3,11 +3,9 @@
 // writes three state_dicts with torch.save and never reads one back into a trainer (code/train.py:342-360).
 //
 // Two launches: (1) a small clear of the 2 n sums; (2) one workgroup per chunk of RD_SNAP_CHUNK bytes, chunks counted from the start
-// of their range (a chunk never straddles two ranges), the grid flat over the chunks of all ranges.  A workgroup finds its range by
-// binary search over the first-chunk column of the device table, copies its chunk -- 16-byte loads and stores on the part where source
-// and destination are both 16-byte aligned, in batches of SNAP_QUADS loads per thread that are all issued before the batch's first
-// store; 4-byte accesses in front and behind, and for the whole chunk when the two sides are aligned differently -- and adds the words
-// it moved into
+// of their range, the grid flat over the chunks of all ranges: the walk of range_walk.h (lookup, alignment split, host-side table
+// check).  A workgroup copies its chunk -- the quads of the split in batches of SNAP_QUADS loads per thread that are all issued before
+// the batch's first store -- and adds the words it moved into
 //     s1 = sum w[i],   s2 = sum (i + 1) w[i]      (mod 2^64, i the word index within the RANGE)
 // with one pair of 64-bit integer atomic adds per workgroup.  Integer addition commutes: the same bits whatever the arrival order.
 // The atomics of one range all land on one address pair, and atomics on one line are served one after the other: with 16 KiB chunks
@@ -15,7 +13,7 @@
 // against a 14 us plain copy of the same bytes; with 64 KiB chunks (1/4 of the atomics) and one 128-byte line of the sums buffer per
 // range (RD_SNAP_SUM_STRIDE: the arenas' pairs in different lines) 21 us, and with both sums in one wave instruction 18 us
 // (profiles/ckpt.md).
-#include "common.h"
+#include "range_walk.h"
 #include "../../include/ramdsir.h"
 
 namespace {
@@ -30,17 +28,8 @@ static_assert(RD_SNAP_CHUNK % (SNAP_BATCH * 16) == 0, "a chunk is a whole number
 static_assert(RD_SNAP_SUM_STRIDE >= 2, "two sums per range");
 static_assert(sizeof(rd_snap_range_t) == 32, "rd_snap_range_t is four 8-byte words");
 
+using namespace rdwalk;
 typedef unsigned long long u64;
-// the ranges and the staging buffer are device allocations: global, not generic, loads and stores
-typedef __attribute__((address_space(1))) unsigned g_u32;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
-    return v;
-}
 
 // the two sums of each of the n ranges; the rest of a range's line is not touched
 __global__ __launch_bounds__(SNAP_THREADS) void snapshot_clear_kernel(u64* __restrict__ sums, int m) {
@@ -59,27 +48,17 @@ __global__ __launch_bounds__(SNAP_THREADS) void snapshot_copy_kernel(const rd_sn
                                                                      int direction) {
     const long long c = blockIdx.x;
     const int t = threadIdx.x;
-    // the last range whose first chunk is <= c: an empty range shares its first chunk with the range behind it and is never chosen
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].chunk0 <= c) lo = mid; else hi = mid - 1;
-    }
+    const int lo = find_range(table, n, c);
     const rd_snap_range_t r = table[lo];
-    const long long w0 = (c - r.chunk0) * SNAP_WORDS;               // first word of this chunk within its range
-    const long long rest = (r.bytes >> 2) - w0;
-    if (c < r.chunk0 || rest <= 0) return;                          // a table that does not match the grid: touch nothing
-    const int len = rest < SNAP_WORDS ? (int)rest : SNAP_WORDS;
+    long long w0;                                                   // first word of this chunk within its range
+    const int len = chunk_len<SNAP_WORDS>(c, r.chunk0, r.bytes >> 2, w0);
+    if (len == 0) return;
     unsigned* const in_range = (unsigned*)r.ptr + w0;
     unsigned* const in_stage = (unsigned*)(staging + r.offset) + w0;
     const g_u32* __restrict__ src = (const g_u32*)(direction == 0 ? in_range : in_stage);
     g_u32* __restrict__ dst = (g_u32*)(direction == 0 ? in_stage : in_range);
-    // [0, head) word by word up to the first 16-byte boundary, then nq whole quads, then [tail, len) word by word; sides that are
-    // aligned differently have no common boundary: head = len
-    int head = (int)((0 - ((uintptr_t)src >> 2)) & 3);
-    if ((((uintptr_t)src ^ (uintptr_t)dst) & 15) != 0) head = len;
-    head = head < len ? head : len;
-    const int nq = (len - head) >> 2, tail = head + 4 * nq;
+    const Split<int> sp = split16(len, src, dst);
+    const int head = sp.head, nq = sp.nq, tail = sp.tail;
     const g_u32x4* __restrict__ s4 = (const g_u32x4*)(src + head);
     g_u32x4* __restrict__ d4 = (g_u32x4*)(dst + head);
     u64 s1 = 0, t2 = 0;
@@ -113,8 +92,8 @@ __global__ __launch_bounds__(SNAP_THREADS) void snapshot_copy_kernel(const rd_sn
         accumulate(w, i, s1, t2);
     }
     __shared__ u64 sh1[SNAP_THREADS / 64], sh2[SNAP_THREADS / 64];
-    s1 = wave_sum_u64(s1);
-    t2 = wave_sum_u64(t2);
+    s1 = wave_sum(s1);
+    t2 = wave_sum(t2);
     if ((t & 63) == 0) { sh1[t >> 6] = s1; sh2[t >> 6] = t2; }
     __syncthreads();
     if (t < 2) {
@@ -136,19 +115,16 @@ extern "C" int rd_snapshot(const rd_snap_range_t* table_host, const rd_snap_rang
     if (n == 0) return 0;
     if (!table_host || !table_dev || !staging || !sums_dev || staging_bytes < 0) return -1;
     if ((uintptr_t)staging % 4 != 0 || (uintptr_t)sums_dev % 8 != 0) return -3;
-    int64_t chunks = 0, end = 0;
-    for (int i = 0; i < n; ++i) {
-        const rd_snap_range_t& r = table_host[i];
+    int64_t end = 0;
+    const int64_t chunks = walk_table<RD_SNAP_CHUNK>(table_host, n, total_chunks, [&](const rd_snap_range_t& r) -> int64_t {
         if (r.bytes < 0 || r.bytes % 4 != 0) return -2;
         if ((uintptr_t)r.ptr % 4 != 0 || r.offset % 4 != 0 || (r.bytes > 0 && !r.ptr)) return -3;
         // offsets ascend in table order: [offset, offset + bytes) starts behind the range in front and ends inside the staging buffer
         if (r.offset < end || r.bytes > staging_bytes || r.offset > staging_bytes - r.bytes) return -4;
         end = r.offset + r.bytes;
-        if (r.chunk0 != chunks) return -5;
-        chunks += (r.bytes + RD_SNAP_CHUNK - 1) / RD_SNAP_CHUNK;
-        if (chunks > 0x7fffffffll) return -5;
-    }
-    if (chunks != total_chunks) return -5;
+        return r.bytes;
+    });
+    if (chunks < 0) return (int)chunks;
     hipStream_t st = (hipStream_t)stream;
     rd_launch(snapshot_clear_kernel, dim3((2 * n + SNAP_THREADS - 1) / SNAP_THREADS), dim3(SNAP_THREADS), 0, st, (u64*)sums_dev, 2 * n);
     if (chunks > 0)

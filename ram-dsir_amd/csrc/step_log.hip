@@ -30,25 +30,6 @@ struct LogArgs {
     int cstart[4];              // chunks [cstart[g], cstart[g + 1]) belong to group g
 };
 
-// s += x * x for a finite x (the product of two converted floats is exact in fp64); a NaN or an infinity is counted instead
-__device__ __forceinline__ void accumulate(float x, double& s, int& bad) {
-    const bool finite = (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;
-    const double d = finite ? (double)x : 0.0;
-    s = d * d + s;
-    bad += finite ? 0 : 1;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // grid (chunks of the call): partial[chunk] = {sum of squares of the finite elements, number of the others}
 __global__ __launch_bounds__(LOG_THREADS) void step_log_partial_kernel(LogArgs a, LogPartial* __restrict__ partial) {
     const int c = blockIdx.x, t = threadIdx.x;

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .range_table import stream_handle
 
 MAX_STEPS = L.ACCUM_MAX_STEPS
 
@@ -74,8 +75,7 @@ def window(grads_list):
 
 def run(grad_ptr, acc_ptr, n, k, steps, inv, stream=None):
     """One rd_grad_accum call; returns its code (0, or the negative validation code: nothing was launched)."""
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    return L.lib().rd_grad_accum(grad_ptr, acc_ptr, n, k, steps, float(inv), s)
+    return L.lib().rd_grad_accum(grad_ptr, acc_ptr, n, k, steps, float(inv), stream_handle(stream))
 
 
 class GradAccum:

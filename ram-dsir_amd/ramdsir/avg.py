@@ -15,7 +15,6 @@ validation and checkpoints then read; the buffers averaged here, and a training-
     WeightAverage.eval_forward()    infer.EvalForward over the averaged bank (its own weight pack)
     WeightAverage.named_ranges()    the averaged ranges for a training-state snapshot (ramdsir/ckpt.py)
 """
-import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
@@ -23,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import engine as E
+from . import range_table as R
 
 MODES = {'ema': L.AVG_EMA, 'uniform': L.AVG_UNIFORM}
 
@@ -50,21 +50,16 @@ def model(avg, live, s, mode, decay=0.999, start=0):
 
 def build_table(entries):
     """[(src pointer, dst pointer, bytes, kind)] -> (the rd_avg_range_t array with its chunk0 column filled in, total chunks)."""
-    arr, chunks = (L.RdAvgRange * max(len(entries), 1))(), 0
-    for e, (src, dst, nbytes, kind) in zip(arr, entries):
-        e.src, e.dst, e.bytes, e.chunk0, e.kind = src, dst, nbytes, chunks, kind
-        chunks += (max(nbytes, 0) + L.AVG_CHUNK - 1) // L.AVG_CHUNK
-    return arr, chunks
+    return R.build(L.RdAvgRange, L.AVG_CHUNK, [dict(src=src, dst=dst, bytes=nbytes, kind=kind) for src, dst, nbytes, kind in entries], 'bytes')
 
 
-def upload_table(arr, n, device):
-    return torch.from_numpy(np.frombuffer(bytes(arr), np.uint8)[:max(n, 1) * C.sizeof(L.RdAvgRange)].copy()).to(device)
+upload_table = R.upload
 
 
 def run(arr, table_dev, n, chunks, iter_ptr, mode, w, start, stream=None):
     """One rd_avg_step call; returns its code (0, or the negative validation code: nothing was launched)."""
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    return L.lib().rd_avg_step(arr, table_dev.data_ptr() if table_dev is not None else None, n, chunks, iter_ptr, mode, float(w), start, s)
+    return L.lib().rd_avg_step(arr, table_dev.data_ptr() if table_dev is not None else None, n, chunks, iter_ptr, mode, float(w), start,
+                               R.stream_handle(stream))
 
 
 class AveragedBank(E.ParamBank):
@@ -105,12 +100,8 @@ class WeightAverage:
         self.live, self.iter = trainer.bank, trainer.ts.iter
         self.bank = AveragedBank(self.live)
         self.ranges = bank_ranges(self.live, self.bank)
-        for name, a, b, _ in self.ranges:
-            nbytes = a.numel() * a.element_size()
-            if nbytes % 4 or not (a.is_contiguous() and b.is_contiguous()):
-                raise ValueError('range %s: %d bytes of a %s tensor (a contiguous multiple of 4 bytes is needed)' % (name, nbytes, a.dtype))
         self.n = len(self.ranges)
-        self.arr, self.chunks = build_table([(a.data_ptr(), b.data_ptr(), a.numel() * a.element_size(), kind) for _, a, b, kind in self.ranges])
+        self.arr, self.chunks = build_table([(a.data_ptr(), b.data_ptr(), R.check_words(name, a, b), kind) for name, a, b, kind in self.ranges])
         self.table_dev = upload_table(self.arr, self.n, self.live.device)       # once: the pointers never move
         self._forward = {}
         self.bn_recal = None                    # FusedTrainer.enable_avg_bn_recal: the avg_bn.BnRecal that re-estimates this model's BatchNorm

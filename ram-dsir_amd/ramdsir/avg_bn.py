@@ -17,7 +17,6 @@ The training is bit-identical with and without it: the capture is a device-to-de
 input, and the pass writes the RecalBank's own buffers.  rd_avg_step keeps averaging the averaged bank's buffers undisturbed, and they
 are what a training-state snapshot holds; nothing of the ring is snapshotted (every epoch's pass uses that epoch's own batches).
 """
-import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
@@ -25,6 +24,7 @@ import torch
 
 from . import _lib as L
 from . import engine as E
+from . import range_table as R
 
 
 # ------------------------------------------------------------------------------------------------ the numpy model of the kernel
@@ -94,14 +94,12 @@ def site_table(sites):
     return arr
 
 
-def upload_table(arr, n, device):
-    return torch.from_numpy(np.frombuffer(bytes(arr), np.uint8)[:max(n, 1) * C.sizeof(L.RdBnRecalSite)].copy()).to(device)
+upload_table = R.upload
 
 
 def run(arr, table_dev, n, max_c, k, eps=E.EPS, stream=None):
     """One rd_bn_recal call; returns its code (0, or the negative validation code: nothing was launched)."""
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    return L.lib().rd_bn_recal(arr, table_dev.data_ptr() if table_dev is not None else None, n, max_c, int(k), float(eps), s)
+    return L.lib().rd_bn_recal(arr, table_dev.data_ptr() if table_dev is not None else None, n, max_c, int(k), float(eps), R.stream_handle(stream))
 
 
 # ------------------------------------------------------------------------------------------------ the plan

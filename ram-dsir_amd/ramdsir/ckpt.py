@@ -20,7 +20,6 @@ ones) and N and the position in the window sit under meta['grad_accum'] (compare
 Checksums of the little-endian uint32 words w[0 .. m) of a range: s1 = sum w[i], s2 = sum (i + 1) w[i], both mod 2^64 (`checksums`
 is the numpy model the kernel equals bit for bit; s2 depends on the order of the words, s1 does not).
 """
-import ctypes as C
 import os
 import queue
 import random
@@ -32,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import range_table as R
 from .optim import DEFAULTS as OPTIM_DEFAULTS               # the reference's optimizer: what a file without the record was taken under
 
 FORMAT, VERSION = 'ramdsir-train-state', 1
@@ -64,22 +64,16 @@ _WEIGHTS = np.arange(1, _BLOCK + 1, dtype=np.uint64)
 # ------------------------------------------------------------------------------------------------------------- rd_snapshot
 def build_table(entries):
     """[(device pointer, bytes, staging offset)] -> (the rd_snap_range_t array with its chunk0 column filled in, total chunks)."""
-    arr, chunks = (L.RdSnapRange * max(len(entries), 1))(), 0
-    for e, (ptr, nbytes, off) in zip(arr, entries):
-        e.ptr, e.bytes, e.offset, e.chunk0 = ptr, nbytes, off, chunks
-        chunks += (max(nbytes, 0) + L.SNAP_CHUNK - 1) // L.SNAP_CHUNK
-    return arr, chunks
+    return R.build(L.RdSnapRange, L.SNAP_CHUNK, [dict(ptr=ptr, bytes=nbytes, offset=off) for ptr, nbytes, off in entries], 'bytes')
 
 
-def upload_table(arr, n, device):
-    return torch.from_numpy(np.frombuffer(bytes(arr), np.uint8)[:max(n, 1) * C.sizeof(L.RdSnapRange)].copy()).to(device)
+upload_table = R.upload
 
 
 def run(arr, table_dev, n, chunks, staging_ptr, staging_bytes, sums_ptr, direction, stream=None):
     """One rd_snapshot call; returns its code (0, or the negative validation code: nothing was launched)."""
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     return L.lib().rd_snapshot(arr, table_dev.data_ptr() if table_dev is not None else None, n, chunks, staging_ptr, staging_bytes,
-                               sums_ptr, direction, s)
+                               sums_ptr, direction, R.stream_handle(stream))
 
 
 def read_sums(buf, n):
@@ -93,9 +87,7 @@ def layout(named):
     """[(name, tensor)] -> the range table without sums: name, dtype, shape, offset (rounded up to ALIGN), bytes; and the blob size."""
     table, off = [], 0
     for name, t in named:
-        nbytes = t.numel() * t.element_size()
-        if nbytes % 4 != 0 or not t.is_contiguous():
-            raise ValueError('range %s: %d bytes of a %s tensor (a contiguous multiple of 4 bytes is needed)' % (name, nbytes, t.dtype))
+        nbytes = R.check_words(name, t)
         table.append(dict(name=name, dtype=str(t.dtype).replace('torch.', ''), shape=list(t.shape), offset=off, bytes=nbytes))
         off = (off + nbytes + ALIGN - 1) // ALIGN * ALIGN
     return table, off

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import range_table as R
 
 CHUNK, THREADS, QUADS = L.LOG_CHUNK, 256, L.LOG_CHUNK // 4 // 256       # rd_grad_guard's first launch (csrc/guard.hip)
 EPS = np.float32(1e-6)
@@ -139,27 +140,20 @@ def bank_ranges(bank, shadows):
 
 def build_table(entries):
     """[(live pointer, shadow pointer, bytes)] -> (the rd_guard_range_t array with its chunk0 column filled in, total chunks)."""
-    arr, chunks = (L.RdGuardRange * max(len(entries), 1))(), 0
-    for e, (live, shadow, nbytes) in zip(arr, entries):
-        e.live, e.shadow, e.bytes, e.chunk0 = live, shadow, nbytes, chunks
-        chunks += (max(nbytes, 0) + L.GUARD_CHUNK - 1) // L.GUARD_CHUNK
-    return arr, chunks
+    return R.build(L.RdGuardRange, L.GUARD_CHUNK, [dict(live=live, shadow=shadow, bytes=nbytes) for live, shadow, nbytes in entries], 'bytes')
 
 
-def upload_table(arr, n, device):
-    return torch.from_numpy(np.frombuffer(bytes(arr), np.uint8)[:max(n, 1) * C.sizeof(L.RdGuardRange)].copy()).to(device)
+upload_table = R.upload
 
 
 def run_guard(desc, stream=None):
     """One rd_grad_guard call; returns its code (0, or the negative validation code: nothing was launched)."""
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    return L.lib().rd_grad_guard(C.byref(desc) if desc is not None else None, s)
+    return L.lib().rd_grad_guard(C.byref(desc) if desc is not None else None, R.stream_handle(stream))
 
 
 def run_sync(arr, table_dev, n, chunks, state_ptr, stream=None):
     """One rd_guard_sync call; returns its code."""
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    return L.lib().rd_guard_sync(arr, table_dev.data_ptr() if table_dev is not None else None, n, chunks, state_ptr, s)
+    return L.lib().rd_guard_sync(arr, table_dev.data_ptr() if table_dev is not None else None, n, chunks, state_ptr, R.stream_handle(stream))
 
 
 class GradGuard:
@@ -182,12 +176,8 @@ class GradGuard:
         self.desc = d
         self.shadows = {k: t.detach().clone() for k, t in bank.buffers.items()}
         self.ranges = bank_ranges(bank, self.shadows)
-        for name, a, b in self.ranges:
-            nbytes = a.numel() * a.element_size()
-            if nbytes % 4 or not (a.is_contiguous() and b.is_contiguous()):
-                raise ValueError('range %s: %d bytes of a %s tensor (a contiguous multiple of 4 bytes is needed)' % (name, nbytes, a.dtype))
         self.n = len(self.ranges)
-        self.arr, self.chunks = build_table([(a.data_ptr(), b.data_ptr(), a.numel() * a.element_size()) for _, a, b in self.ranges])
+        self.arr, self.chunks = build_table([(a.data_ptr(), b.data_ptr(), R.check_words(name, a, b)) for name, a, b in self.ranges])
         self.table_dev = upload_table(self.arr, self.n, dev)            # once: the pointers never move
 
     def settings(self):

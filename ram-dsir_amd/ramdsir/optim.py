@@ -22,9 +22,9 @@ import ctypes as C
 import math
 
 import numpy as np
-import torch
 
 from . import _lib as L
+from . import range_table as R
 
 CHUNK = L.OPT_CHUNK
 SCHEDULES = {'poly': L.OPT_POLY, 'cosine': L.OPT_COSINE, 'constant': L.OPT_CONSTANT}
@@ -52,11 +52,8 @@ def check_settings(weight_decay, wd_mode, lr_schedule, warmup_iters, enc_lr_mult
 
 def make_table(entries):
     """[(first, count, lr_mult, weight_decay)] -> (the rd_optim_range_t array with its chunk0 column filled in, total chunks)."""
-    arr, chunks = (L.RdOptimRange * max(len(entries), 1))(), 0
-    for e, (first, count, lr_mult, wd) in zip(arr, entries):
-        e.first, e.count, e.lr_mult, e.weight_decay, e.chunk0 = int(first), int(count), float(lr_mult), float(wd), chunks
-        chunks += (max(int(count), 0) + CHUNK - 1) // CHUNK
-    return arr, chunks
+    return R.build(L.RdOptimRange, CHUNK, [dict(first=int(first), count=int(count), lr_mult=float(lr_mult), weight_decay=float(wd))
+                                           for first, count, lr_mult, wd in entries], 'count')
 
 
 def bank_entries(bank, enc_lr_mult=0.5, weight_decay=0.0):
@@ -85,7 +82,7 @@ def build_table(bank, enc_lr_mult=0.5, weight_decay=0.0):
 
 
 def upload_table(arr, device):
-    return torch.from_numpy(np.frombuffer(bytes(arr), np.uint8).copy()).to(device)
+    return R.upload(arr, len(arr), device)
 
 
 def schedule_model(it, base_lr, total, schedule='poly', warmup=0):
@@ -125,9 +122,8 @@ def decay_model(param, grad, lr, lr_mult, decay, wd_mode='decoupled'):
 
 def run_step(desc, arr, table_dev, n_ranges, chunks, guard_ptr=None, stream=None):
     """One rd_optim_step call; returns its code (0, or the negative validation code: nothing was launched)."""
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     return L.lib().rd_optim_step(C.byref(desc) if desc is not None else None, arr, table_dev.data_ptr() if table_dev is not None else None,
-                                 n_ranges, chunks, guard_ptr, s)
+                                 n_ranges, chunks, guard_ptr, R.stream_handle(stream))
 
 
 class GroupedAdam:

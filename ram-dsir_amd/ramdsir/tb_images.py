@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .range_table import stream_handle
 
 PALETTE = np.array([[0, 0, 0], [128, 0, 0], [0, 128, 0], [128, 128, 0], [0, 0, 128], [128, 0, 128], [0, 128, 128], [128, 128, 128],
                     [64, 0, 0], [192, 0, 0], [64, 128, 0], [192, 128, 0], [64, 0, 128], [192, 0, 128], [64, 128, 128],
@@ -150,8 +151,8 @@ def compose(specs, out, workspace, stream=None):
     lib = L.lib()
     if off > out.numel() or out.dtype != torch.uint8 or workspace.numel() * workspace.element_size() < lib.rd_tb_grids_workspace(len(specs)):
         raise ValueError('output (%d bytes needed) or workspace too small' % off)
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    L.check(lib.rd_tb_grids(arr, len(specs), workspace.data_ptr(), workspace.numel() * workspace.element_size(), s), 'rd_tb_grids')
+    L.check(lib.rd_tb_grids(arr, len(specs), workspace.data_ptr(), workspace.numel() * workspace.element_size(), stream_handle(stream)),
+            'rd_tb_grids')
     return layout
 
 

@@ -313,6 +313,22 @@ def test_guard_sync_moves_the_bytes_in_the_direction_of_the_flag(count):
     ar.sync(skip=False)
 
 
+def test_guard_sync_at_the_chunk_edges():
+    """The sizes around a chunk of the walk (csrc/range_walk.h) that the test above does not reach -- one word short of a chunk, a
+    whole chunk, and three chunks and a ragged fourth -- each at the 16 pairings of live and shadow offsets mod 16, with an empty
+    range between two full ones; both directions."""
+    CH = L.GUARD_CHUNK
+    specs = [(nb, lo, so) for nb in (CH - 4, CH, 3 * CH + 20) for lo in (0, 4, 8, 12) for so in (0, 4, 8, 12)]
+    specs[7:7] = [(0, 0, 0)]
+    ar = SyncArena(specs, seed=49)
+    assert ar.n == 49 and ar.chunks == 16 * (1 + 1 + 4)
+    ar.sync(skip=False)
+    ar.live.copy_(torch.from_numpy(np.where(ar.live_host == SENT, ar.live_host, ar.live_host ^ 0x5A).astype(np.uint8)))
+    ar.live_host[:] = ar.live.cpu().numpy()
+    ar.sync(skip=True)
+    ar.sync(skip=False)
+
+
 def test_guard_sync_validation_codes_and_the_empty_call():
     specs = [(16384 + 4, 0, 0), (0, 0, 0), (64, 4, 8)]
     ar = SyncArena(specs, seed=5)
