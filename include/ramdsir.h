@@ -1037,6 +1037,55 @@ int rd_optim_step(const rd_optim_t* p, const rd_optim_range_t* table_host, const
 #define RD_ACCUM_MAX_N (1ll << 40)
 int rd_grad_accum(float* grad, float* acc, int64_t n, int32_t k, int32_t steps, float inv_steps, void* stream);
 
+/* Per-tensor histograms (train.py --tb_hist, ramdsir/tb_hist.py), csrc/hist.hip: what TensorBoard's histogram dashboard shows of the
+ * four arenas -- one histogram and one statistics record per range of a table, computed where the arenas live.  No reference
+ * counterpart: the reference writes scalars and images only (code/train.py:298-329).
+ *
+ * The table: n <= RD_HIST_MAX_RANGES records {src, count, chunk0} in the convention of csrc/range_walk.h (see rd_snapshot): the same
+ * records on the host (read for validation only) and in device memory (uploaded once), range i cut into chunks of RD_HIST_CHUNK
+ * ELEMENTS from its start, chunk0 the number of chunks of the ranges in front of it.  src is an absolute device pointer of any
+ * 4-byte alignment, so one table spans several arenas; count may be 0.  The limits: n_limits doubles, strictly ascending and finite,
+ * 2 <= n_limits <= RD_HIST_MAX_LIMITS, the same values at limits_host (validation) and limits_dev (the kernel): they are data, not
+ * code, so the kernel compares against the very doubles the caller's numpy holds.
+ *
+ * A finite element v falls into bucket b = min(#{i : limits[i] <= (double)v}, n_limits - 1): TensorFlow's upper_bound rule, bucket b
+ * has the upper edge limits[b], there are n_limits buckets; the comparison is between the widened float and the double limit, exact,
+ * == np.searchsorted(limits, v.astype(float64), side='right') clamped.  Per range i: counts[i][n_limits] (uint32) and stats[i] =
+ * {min, max, sum, sum_squares over the finite elements in fp64; num = their number; nonfinite = the number of NaN and +-Inf elements,
+ * which enter nothing else}.  An empty range, or one without a finite element, gives all-zero counts and num = min = max = sum =
+ * sum_squares = 0.
+ *
+ * Three launches on `stream`: (1) counts <- 0 (the caller's contents are irrelevant); (2) a flat grid over the chunks of all ranges,
+ * one workgroup per chunk: an LDS histogram under integer LDS atomics, its non-empty bins added to counts[i] with uint32 global vector
+ * atomics (integer addition: the bits do not depend on the order), the statistics of the chunk -> partial[chunk] without atomics, in
+ * an order fixed by the indices; (3) one wave per range adds the partials of its chunks (lane l takes l, l + 64, ... ascending, then
+ * the fixed xor tree) -- rd_step_log's decomposition.  ramdsir/tb_hist.py model() is the numpy model: counts, num, nonfinite, min,
+ * max equal on any data; sum and sum_squares bit for bit where the sums are exact in fp64, otherwise within the bound of the
+ * summation length.  workspace: rd_hist_workspace(total_chunks) bytes, 8-byte aligned, non-null, contents irrelevant before and after.
+ *
+ * Returns, before anything is launched and without dereferencing a device pointer: -1 a null table / limits / counts / stats /
+ * workspace, n outside 1..RD_HIST_MAX_RANGES, or a misaligned pointer (table_dev, limits_dev, stats, workspace 8 bytes, counts 4);
+ * -2 n_limits outside 2..RD_HIST_MAX_LIMITS, limits not strictly ascending or not finite; -3 a range with a null or non-4-byte-aligned
+ * src, or a count that is negative or above 2^31 - 1; -5 a chunk0 column or total_chunks that does not match the counts.  Nothing is
+ * allocated, synchronised or copied; every launch goes through the library's one launch site. */
+#define RD_HIST_CHUNK 16384
+#define RD_HIST_MAX_LIMITS 4096
+#define RD_HIST_MAX_RANGES 4096
+typedef struct {
+    const float* src;           /* device start of the range (absolute) */
+    int64_t count;              /* elements */
+    int64_t chunk0;             /* first chunk of the range in the flat grid */
+} rd_hist_range_t;
+typedef struct {
+    double min, max, sum, sum_squares;      /* over the finite elements */
+    int64_t num;                /* finite elements */
+    int64_t nonfinite;          /* NaN and +-Inf elements */
+} rd_hist_stats_t;
+int64_t rd_hist_workspace(int64_t total_chunks);
+int rd_hist(const rd_hist_range_t* table_host, const rd_hist_range_t* table_dev, int n, int64_t total_chunks,
+            const double* limits_host, const double* limits_dev, int n_limits, uint32_t* counts, rd_hist_stats_t* stats,
+            void* workspace, void* stream);
+
 /* crc32c (Castagnoli) of n HOST bytes, continuing from `seed` (the crc of the bytes in front; 0 for none) -- the checksum of the
  * TFRecord framing of utils/tfevents.py, whose pure-Python loop runs at about a megabyte per second against image records of hundreds
  * of kilobytes.  Plain table-driven C++ on the host (csrc/crc32c.hip): no GPU involved.  No reference counterpart (tensorboardX's crc32c). */

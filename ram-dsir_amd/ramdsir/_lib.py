@@ -214,6 +214,21 @@ class RdOptimRange(C.Structure):
 
 ACCUM_MAX_STEPS = 65536                                             # RD_ACCUM_MAX_STEPS
 
+HIST_CHUNK = 16384                                                  # RD_HIST_CHUNK (elements)
+HIST_MAX_LIMITS = 4096                                              # RD_HIST_MAX_LIMITS
+HIST_MAX_RANGES = 4096                                              # RD_HIST_MAX_RANGES
+
+
+class RdHistRange(C.Structure):
+    """rd_hist_range_t (include/ramdsir.h): one tensor of rd_hist's table, an absolute device pointer and an element count."""
+    _fields_ = [('src', vp), ('count', i64), ('chunk0', i64)]
+
+
+class RdHistStats(C.Structure):
+    """rd_hist_stats_t (include/ramdsir.h): the statistics record rd_hist writes per range."""
+    _fields_ = [('min', C.c_double), ('max', C.c_double), ('sum', C.c_double), ('sum_squares', C.c_double), ('num', i64),
+                ('nonfinite', i64)]
+
 
 class RdLaunch(C.Structure):
     """rd_launch_t (include/ramdsir.h): one entry of a native launch list."""
@@ -307,6 +322,8 @@ _SIGS = {
     'rd_guard_sync': (C.c_int, [C.POINTER(RdGuardRange), vp, C.c_int, i64, vp, vp]),
     'rd_optim_step': (C.c_int, [C.POINTER(RdOptim), C.POINTER(RdOptimRange), vp, C.c_int, i64, vp, vp]),
     'rd_grad_accum': (C.c_int, [fp, fp, i64, i32, i32, f32, vp]),
+    'rd_hist_workspace': (i64, [i64]),
+    'rd_hist': (C.c_int, [C.POINTER(RdHistRange), vp, C.c_int, i64, vp, vp, C.c_int, vp, vp, vp, vp]),
     'rd_crc32c':(C.c_uint32, [vp, C.c_size_t, C.c_uint32]),
     'rd_box_probe': (C.c_int, [C.c_int, vp, vp, i64, vp]),
     'rd_fundus_batch': (C.c_int, [C.POINTER(RdFundusBatch), C.POINTER(RdFundusSample), C.c_int, vp]),

@@ -32,6 +32,7 @@ class FusedTrainer:
         self._optim = None
         self._accum = None
         self._bn_recal, self._bn_capture = None, False
+        self._hist, self._hist_armed, self._hist_pending = None, None, None
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         if self.world > 1:
             # identical initial weights on every rank (DataParallel broadcasts replica 0's, train.py:205-208)
@@ -103,13 +104,15 @@ class FusedTrainer:
         average (every step, once enabled) share it: one closure per step runs whichever of the three apply, in the order step log,
         averaging, image compose -- the two per-step launches of a few microseconds first, the compose and the start of its copy to
         the host last.  All three only read the step's buffers, so the order changes no result.  Nothing is armed when none applies.
-        A step armed with arm_bn_capture() (--avg_bn_recal) joins them with one copy of its input, behind the averaging."""
+        A step armed with arm_bn_capture() (--avg_bn_recal) joins them with one copy of its input, behind the averaging; a step armed
+        with arm_tb_hist() (--tb_hist) ends the hook with the rd_hist call over the arenas and the start of its copy."""
         tb, self._tb_hook = self._tb_hook, None
+        hist, self._hist_armed = self._hist_armed, None
         log, avg = self._log, self._avg
         cap, self._bn_capture = (self._bn_recal if self._bn_capture else None), False
         if avg is not None and self._accum is not None and not self._accum.next_is_boundary():
             avg = None                                      # rd_avg_step reads the counter, which moves at a window's last step only
-        if tb is None and log is None and avg is None and cap is None:
+        if tb is None and log is None and avg is None and cap is None and hist is None:
             return
 
         def hook(slot):
@@ -121,7 +124,38 @@ class FusedTrainer:
                 cap.capture(slot)                           # --avg_bn_recal: the clean half of the step's input into the ring
             if tb is not None:
                 tb(slot)
+            if hist is not None:
+                self._hist_pending = self._hist.enqueue(torch.cuda.current_stream().cuda_stream, copy=hist == 'copy')
         self.ts.arm_after_step(hook)
+
+    def enable_tb_hist(self, what=('weights', 'grads')):
+        """Builds the histogram state of train.py --tb_hist (ramdsir/tb_hist.py): the range table over every parameter tensor of the
+        arenas named in `what` (weights, grads, adam_m, adam_v), the uploaded bucket limits, the device output, the workspace.  Nothing
+        runs until a step is armed with arm_tb_hist().  Only reads the arenas: training is bit-identical with and without it.  Returns
+        the tb_hist.TbHist.  Not with use_graph=True."""
+        if self._graphs:
+            self.ts.refuse_fixed_list('enable_tb_hist', ['the per-tensor histograms behind the step (rd_hist)'])
+        from . import tb_hist
+        self._hist = tb_hist.TbHist(self.bank, what)
+        return self._hist
+
+    def arm_tb_hist(self, copy=True):
+        """The next step() is followed by ONE rd_hist call on the main stream -- behind the whole tail (Adam, repack, guard sync, the
+        weight average), in front of the upload of the next mask: `grads` still holds this step's gradient (the one the step log's
+        health pass reads), `params` and the moments are the updated ones -- and, with copy, by the copy of its result to pinned host
+        memory; take_tb_hist() then returns the pending result.  A data-parallel rank that does not write passes copy=False: the
+        launch runs (every rank enqueues the same step), nothing is copied.  A step that is not armed runs no launch and no call."""
+        self._refuse_graphs('arm_tb_hist')
+        if self._hist is None:
+            raise RuntimeError('arm_tb_hist: enable_tb_hist() first')
+        self._hist_armed = 'copy' if copy else 'launch'
+
+    def take_tb_hist(self):
+        """The tb_hist.Pending of the last armed step (its fetch() waits for the copy), once."""
+        pending, self._hist_pending = self._hist_pending, None
+        if pending is None:
+            raise RuntimeError('take_tb_hist: no armed step (with copy) has run')
+        return pending
 
     def enable_avg_bn_recal(self, K):
         """BatchNorm re-estimation of the averaged model (ramdsir/avg_bn.py; needs enable_avg_weights first): a device ring of K

@@ -29,7 +29,10 @@ reference's one hard-coded optimizer line (Adam without decay, lr / 2 on the enc
 Adam whose ranges, decay and schedule live on the device (ramdsir/optim.py, rd_optim_step); their defaults ARE that line; (ix)
 --accum_steps N applies the optimizer at every N-th iteration, on the mean of the N micro-batch gradients (ramdsir/accum.py,
 rd_grad_accum: one HIP launch per iteration into a second gradient arena) -- the effective batch is N times the reference's per-domain
-tables (code/train.py:35-45), which stay as they are; the schedule counts updates, the loop counts iterations.
+tables (code/train.py:35-45), which stay as they are; the schedule counts updates, the loop counts iterations; (x) --tb_hist N writes
+one TensorBoard histogram per parameter tensor of the weights and gradients (--tb_hist_what: also the two Adam moments) every N
+iterations, counted by one HIP call over the arenas behind the step and written by the writer thread (ramdsir/tb_hist.py, rd_hist); the
+reference writes scalars and images only (code/train.py:298-329).
 """
 import argparse
 import os
@@ -119,6 +122,13 @@ def parse_args(argv=None):
                    help='also write the reference\'s TensorBoard image grids (input, RAM-mixed input, restored image, predictions, ground '
                         'truth) of rank 0\'s batch every N iterations (100 as in the reference when N is omitted), composed by one HIP '
                         'call from the step\'s buffers and encoded by a writer thread; off by default')
+    p.add_argument('--tb_hist', type=int, nargs='?', const=100, default=0, metavar='N',
+                   help='also write one TensorBoard histogram per parameter tensor (tags <kind>/<module>.<key>, TensorFlow\'s default '
+                        'buckets) every N iterations (100 when N is omitted): one HIP call over the arenas behind the step (ramdsir/'
+                        'tb_hist.py, rd_hist), one copy, trimmed and encoded by a writer thread; non-finite elements are left out and '
+                        'reported as hist_nonfinite/<kind>; --norm bn only, not with --accum_steps; off by default')
+    p.add_argument('--tb_hist_what', type=str, default=None, metavar='LIST',
+                   help='with --tb_hist: a comma list over weights,grads,adam_m,adam_v (default weights,grads)')
     p.add_argument('--tb_every_iter', action='store_true',
                    help='write the seven TensorBoard scalars at EVERY iteration, as the reference does (train.py:298-304, 467-473), without a '
                         'host synchronisation per step: one small HIP launch behind each step appends them to a device-resident ring '
@@ -591,6 +601,16 @@ def record_is_finite(rec):
         and all(np.isfinite(v) for v in rec['norms'])
 
 
+def uses_tb_hist(args):
+    return args.tb_hist > 0
+
+
+def tb_hist_what(args):
+    """--tb_hist_what as a tuple of kinds; ValueError for an unknown, repeated or empty one (no GPU call: the module only parses)."""
+    from ramdsir import tb_hist
+    return tb_hist.DEFAULT_WHAT if args.tb_hist_what is None else tb_hist.parse_what(args.tb_hist_what)
+
+
 def check_args(args, world):
     """Every flag combination this script refuses, and nothing else: no GPU call, no file, no process."""
     if not (args.ram and args.rec):
@@ -668,6 +688,18 @@ def check_args(args, world):
     if uses_accum(args) and uses_step_log(args):
         raise ValueError('--accum_steps does not go with --tb_every_iter / --tb_health: the rows of the per-step ring are keyed by the '
                          'optimizer\'s counter, which moves once per window')
+    if args.tb_hist < 0:
+        raise ValueError('--tb_hist takes a positive interval, got %d' % args.tb_hist)
+    if args.tb_hist_what is not None and not uses_tb_hist(args):
+        raise ValueError('--tb_hist_what chooses the arenas of the histograms: it needs --tb_hist')
+    if uses_tb_hist(args):
+        tb_hist_what(args)
+        if args.norm != 'bn':
+            raise ValueError('--tb_hist reads the fused step\'s parameter, gradient and moment arenas: --norm %s trains through the modules, '
+                             'which have no arenas behind a fused step' % args.norm)
+        if uses_accum(args):
+            raise ValueError('--tb_hist does not go with --accum_steps: inside a window the gradient arena holds a micro-batch gradient '
+                             'that belongs to the accumulator, not the gradient of an update')
 
 
 class TrainLog:
@@ -681,7 +713,7 @@ class TrainLog:
         self.guard_mark = guard.read() if guard is not None else None      # (behind a --resume restore: the counts continue)
         # --tb_images: one writer thread owns the event file (scalars go through its queue too, so the records keep the order of the
         # calls); without the flag the direct writer, record for record what it always wrote
-        Writer = QueuedWriter if args.tb_images else SummaryWriter
+        Writer = QueuedWriter if (args.tb_images or uses_tb_hist(args)) else SummaryWriter
         self.writer = Writer(os.path.join(args.save_path, 'log')) if self.rank0 else None
         self.first_bad = None                               # --tb_health: the first iteration with non-finite values, named once
         self.t_mark, self.it_mark = None, 0                 # the throughput clock starts at iteration 5
@@ -717,7 +749,7 @@ class TrainLog:
                   'not moved since iteration %d' % (steps, iter_num, iter_num - steps))
         return guard_suffix(g), guard_pairs(g)
 
-    def after_step(self, iter_num, log_images):
+    def after_step(self, iter_num, log_images, log_hist=False):
         """Behind the step of iteration iter_num.  With the ring, it is read where the loop synchronises anyway (the logging
         iterations), in front of image records (they follow the scalars of their own iteration) and when it is full -- all
         functions of iter_num alone, so every rank drains at the same iterations."""
@@ -741,6 +773,8 @@ class TrainLog:
                 self.writer.add_scalars_at(iter_num, scalar_pairs(lr_now, l) + pairs)
         if log_images:                                      # behind the scalars of the iteration, in the reference's tag order
             self.writer.add_images_at(iter_num, trainer.take_tb_images())
+        if log_hist:                                        # --tb_hist: the writer thread waits for the copy, trims and encodes
+            self.writer.add_histograms_at(iter_num, trainer.take_tb_hist())
         if iter_num + 1 == 5:                               # end-to-end throughput (files -> DataLoader -> H2D -> step), start-up excluded
             torch.cuda.synchronize()
             self.t_mark, self.it_mark = time.time(), iter_num + 1
@@ -762,6 +796,11 @@ class TrainLog:
             print('tb_images: %d image records at %d iterations; writer thread per logging iteration: wait for the copy %.2f ms, PNG %.2f ms, '
                   'crc32c + framing %.2f ms, file write %.2f ms' % (sec['records'], n, 1e3 * sec['wait'] / n, 1e3 * sec['png'] / n,
                                                                     1e3 * sec['crc'] / n, 1e3 * sec['write'] / n))
+        if uses_tb_hist(self.args) and self.writer.seconds['histo']['calls']:
+            sec, n = self.writer.seconds['histo'], self.writer.seconds['histo']['calls']
+            print('tb_hist: %d histogram records at %d iterations; writer thread per logging iteration: wait for the copy + trimming '
+                  '%.2f ms, protobuf + crc32c + framing %.2f ms, file write %.2f ms' % (sec['records'], n, 1e3 * sec['wait'] / n,
+                                                                                       1e3 * sec['encode'] / n, 1e3 * sec['write'] / n))
 
 
 def build_trainer(args, rank, raw, resident, batch_sizes, max_len):
@@ -939,9 +978,12 @@ def train_epoch(args, trainer, loaders, resident, log, iter_num, recal=None, epo
             trainer.arm_tb_images()                     # this step also composes the grids of its batch and starts their copy
         if recal is not None and iter_num >= first_captured:
             trainer.arm_bn_capture()                    # ... and this one leaves the clean half of its input in the ring
+        log_hist = args.tb_hist > 0 and iter_num % args.tb_hist == 0
+        if log_hist:
+            trainer.arm_tb_hist(copy=log.rank0)         # every rank enqueues the same step; rank 0 copies and writes
         trainer.step(*cur, next_batch=nxt)
         cur = nxt
-        log.after_step(iter_num, log_images)
+        log.after_step(iter_num, log_images, log_hist and log.rank0)
         iter_num += 1
         if args.max_iters and iter_num >= args.max_iters:
             break
@@ -1000,6 +1042,12 @@ def main(args):
     if accum is not None and rank == 0:
         print(accum_line(args.accum_steps, *accum_totals(args, max_len)))
     state_io = open_state(args, trainer, (bsl, domain_idx_list, H, W, total_iters), resume_state) if uses_ckpt(args) else None
+    # --tb_hist: the range table over the arenas, the bucket limits, the output and the pinned buffer; no state of its own
+    if uses_tb_hist(args):
+        hist = trainer.enable_tb_hist(tb_hist_what(args))
+        if rank == 0:
+            print('tb_hist: %d histograms (%s) of %d buckets every %d iterations, %.1f MB copied per logging iteration'
+                  % (hist.n, ','.join(hist.what), hist.n_limits, args.tb_hist, hist.copy_bytes / 1e6))
     if val is not None:
         val.bind(trainer)
         if avg is not None and val.mode != 'fused':

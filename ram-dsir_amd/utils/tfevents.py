@@ -1,12 +1,14 @@
-"""Minimal TensorBoard event-file writer for scalars and images: what the reference's `tensorboardX.SummaryWriter(save_path + '/log')`
+"""Minimal TensorBoard event-file writer for scalars, images and histograms: what the reference's `tensorboardX.SummaryWriter(save_path + '/log')`
 produces for `writer.add_scalar(tag, value, iter_num)` (code/train.py:298-304, 467-473, 538) and `writer.add_image(tag, grid, iter_num)`
 (train.py:306-329, 475-496).  tensorboardX / tensorboard are not installed here, so the three pieces are written out by hand:
 
   * TFRecord framing: uint64 length | masked crc32c(length) | payload | masked crc32c(payload), little endian;
   * crc32c (Castagnoli, reflected polynomial 0x82F63B78) with TensorFlow's mask ((crc >> 15 | crc << 17) + 0xa282ead8);
   * protobuf wire format of  Event { double wall_time = 1; int64 step = 2; string file_version = 3; Summary summary = 5; }
-    Summary { repeated Value value = 1; }   Value { string tag = 1; float simple_value = 2; Image image = 4; }
-    Image { int32 height = 1; int32 width = 2; int32 colorspace = 3; bytes encoded_image_string = 4; }.
+    Summary { repeated Value value = 1; }   Value { string tag = 1; float simple_value = 2; Image image = 4; HistogramProto histo = 5; }
+    Image { int32 height = 1; int32 width = 2; int32 colorspace = 3; bytes encoded_image_string = 4; }
+    HistogramProto { double min = 1; double max = 2; double num = 3; double sum = 4; double sum_squares = 5;
+                     repeated double bucket_limit = 6 [packed]; repeated double bucket = 7 [packed]; }.
 
 The first record of a file is Event{wall_time, file_version: "brain.Event:2"}; the file name follows TensorBoard's
 `events.out.tfevents.<unix time>.<hostname>` pattern so that `tensorboard --logdir <save_path>/log` picks it up.
@@ -14,6 +16,8 @@ Image summaries take the finished uint8 HWC grid (train.py --tb_images composes 
 make_grid and tensorboardX's float -> uint8 conversion) and encode it as PNG with Pillow, as tensorboardX does.  The checksum of such a
 record (hundreds of kilobytes) goes through the HIP library's host routine rd_crc32c when the library is loadable; the pure-Python
 loop below is the fallback and the reference of the tests.
+Histogram summaries (train.py --tb_hist; no reference counterpart -- the reference writes scalars and images only) take finished
+buckets under tensorboardX's add_histogram_raw: ramdsir/tb_hist.py counts them on the GPU and trims them on the writer thread.
 """
 import io
 import os
@@ -98,8 +102,18 @@ def encode_png(img_hwc_uint8):
     return a.shape[0], a.shape[1], (3 if a.ndim == 3 else 1), buf.getvalue()
 
 
-def encode_event(wall_time, step=None, file_version=None, scalars=None, images=None):
-    """scalars: list of (tag, float); images: list of (tag, height, width, colorspace, png bytes)."""
+def encode_histo(mn, mx, num, total, sum_squares, bucket_limits, bucket_counts):
+    """The bytes of one HistogramProto: five doubles, then the limits and the counts as packed repeated doubles."""
+    limits, counts = [float(v) for v in bucket_limits], [float(v) for v in bucket_counts]
+    if len(limits) != len(counts):
+        raise ValueError('a histogram has one count per limit, got %d limits and %d counts' % (len(limits), len(counts)))
+    h = b''.join(_key(f, 1) + struct.pack('<d', float(v)) for f, v in enumerate((mn, mx, num, total, sum_squares), 1))
+    return h + _bytes_field(6, struct.pack('<%dd' % len(limits), *limits)) + _bytes_field(7, struct.pack('<%dd' % len(counts), *counts))
+
+
+def encode_event(wall_time, step=None, file_version=None, scalars=None, images=None, histos=None):
+    """scalars: list of (tag, float); images: list of (tag, height, width, colorspace, png bytes); histos: list of (tag, min, max, num,
+    sum, sum_squares, bucket limits, bucket counts)."""
     ev = _key(1, 1) + struct.pack('<d', wall_time)
     if step is not None:
         ev += _key(2, 0) + _varint(int(step))
@@ -116,6 +130,11 @@ def encode_event(wall_time, step=None, file_version=None, scalars=None, images=N
         for tag, h, w, cs, png in images:
             im = _key(1, 0) + _varint(h) + _key(2, 0) + _varint(w) + _key(3, 0) + _varint(cs) + _bytes_field(4, bytes(png))
             summ += _bytes_field(1, _bytes_field(1, tag.encode()) + _bytes_field(4, im))
+        ev += _bytes_field(5, summ)
+    if histos:
+        summ = b''
+        for h in histos:
+            summ += _bytes_field(1, _bytes_field(1, h[0].encode()) + _bytes_field(5, encode_histo(*h[1:])))
         ev += _bytes_field(5, summ)
     return ev
 
@@ -155,6 +174,14 @@ class SummaryWriter(object):
         if t - self._last > self._flush_secs:
             self.flush()
 
+    def add_histogram_raw(self, tag, min, max, num, sum, sum_squares, bucket_limits, bucket_counts, global_step=None, walltime=None):
+        """One Summary.Value{tag, histo} record from finished buckets (tensorboardX's name and argument order): bucket_counts[i] values
+        lie in the bucket whose upper edge is bucket_limits[i]."""
+        t = time.time() if walltime is None else walltime
+        self._f.write(frame(encode_event(t, step=global_step, histos=[(tag, min, max, num, sum, sum_squares, bucket_limits, bucket_counts)])))
+        if t - self._last > self._flush_secs:
+            self.flush()
+
     def flush(self):
         self._f.flush()
         self._last = time.time()
@@ -166,11 +193,14 @@ class SummaryWriter(object):
 
 
 class QueuedWriter(SummaryWriter):
-    """A SummaryWriter whose records are encoded and written by ONE thread that owns the file (train.py --tb_images): the training
+    """A SummaryWriter whose records are encoded and written by ONE thread that owns the file (train.py --tb_images / --tb_hist): the training
     thread only enqueues.  add_scalars_at takes its wall time at the call, as the direct writer does; add_images_at(step, fetch)
     takes a callable that returns [(tag, uint8 HWC array)] when the data has arrived (ramdsir.tb_images.Pending: it waits for the
     event behind the device-to-host copy) -- PNG encoding (zlib, Pillow: both release the GIL), checksums and the write happen in the
-    thread.  Records appear in the order of the calls.  close() drains the queue; an error in the thread is raised there."""
+    thread.  add_histograms_at(step, fetch) is the third kind of item: fetch() returns (histograms, scalars) -- [(tag, min, max, num,
+    sum, sum_squares, bucket limits, bucket counts)] and [(tag, value)] -- when the data has arrived (ramdsir.tb_hist.Pending), written
+    as one record each, the histograms first.  Records appear in the order of the calls.  close() drains the queue; an error in the
+    thread is raised there."""
 
     def __init__(self, logdir, flush_secs=30):
         import queue
@@ -178,6 +208,7 @@ class QueuedWriter(SummaryWriter):
         SummaryWriter.__init__(self, logdir, flush_secs)
         self._q, self._err = queue.Queue(), None
         self.seconds = dict(wait=0.0, png=0.0, crc=0.0, write=0.0, records=0, calls=0)      # host time of the image records (profiles/tb_images.md)
+        self.seconds['histo'] = dict(wait=0.0, encode=0.0, write=0.0, records=0, calls=0)  # ... and of the histogram records (profiles/tb_hist.md)
         self._t = threading.Thread(target=self._drain, name='tfevents-writer', daemon=True)
         self._t.start()
 
@@ -190,6 +221,29 @@ class QueuedWriter(SummaryWriter):
     def add_image(self, tag, img_hwc_uint8, global_step=None, walltime=None):
         self.add_images_at(global_step, lambda: [(tag, img_hwc_uint8)], walltime)
 
+    def add_histograms_at(self, global_step, fetch, walltime=None):
+        self._q.put(('histos', global_step, fetch, time.time() if walltime is None else walltime))
+
+    def add_histogram_raw(self, tag, min, max, num, sum, sum_squares, bucket_limits, bucket_counts, global_step=None, walltime=None):
+        h = (tag, min, max, num, sum, sum_squares, list(bucket_limits), list(bucket_counts))
+        self.add_histograms_at(global_step, lambda: ([h], []), walltime)
+
+    def _write_histos(self, step, fetch, t):
+        sec = self.seconds['histo']
+        t0 = time.perf_counter()
+        histos, scalars = fetch()
+        t1 = time.perf_counter()
+        recs = [frame(encode_event(t, step=step, histos=[h])) for h in histos]
+        recs += [frame(encode_event(t, step=step, scalars=[p])) for p in scalars]
+        t2 = time.perf_counter()
+        self._f.write(b''.join(recs))
+        t3 = time.perf_counter()
+        sec['wait'] += t1 - t0                      # the copy's event and the trimming (ramdsir.tb_hist.Pending.fetch)
+        sec['encode'] += t2 - t1                    # protobuf, crc32c, framing
+        sec['write'] += t3 - t2
+        sec['records'] += len(recs)
+        sec['calls'] += 1
+
     def _drain(self):
         while True:
             item = self._q.get()
@@ -201,6 +255,11 @@ class QueuedWriter(SummaryWriter):
                 kind, step, payload, t = item
                 if kind == 'scalars':
                     SummaryWriter.add_scalars_at(self, step, payload, t)
+                    continue
+                if kind == 'histos':
+                    self._write_histos(step, payload, t)
+                    if t - self._last > self._flush_secs:
+                        self.flush()
                     continue
                 sec = self.seconds
                 t0 = time.perf_counter()
@@ -267,8 +326,9 @@ def _fields(buf):
 
 
 def read_events(path):
-    """-> list of dicts {wall_time, step, file_version, scalars: [(tag, value)], images: [(tag, height, width, colorspace, png bytes)]};
-    every CRC is verified."""
+    """-> list of dicts {wall_time, step, file_version, scalars: [(tag, value)], images: [(tag, height, width, colorspace, png bytes)],
+    histos: [(tag, min, max, num, sum, sum_squares, bucket limits, bucket counts)] (the last two as tuples of floats)}; every CRC is
+    verified."""
     out = []
     with open(path, 'rb') as f:
         data = f.read()
@@ -282,7 +342,7 @@ def read_events(path):
         if c1 != masked_crc(head) or c2 != masked_crc(payload) or len(payload) != n:
             raise ValueError('corrupt record at byte %d' % pos)
         pos += 16 + n
-        ev = dict(wall_time=None, step=0, file_version=None, scalars=[], images=[])
+        ev = dict(wall_time=None, step=0, file_version=None, scalars=[], images=[], histos=[])
         for field, wire, v in _fields(payload):
             if field == 1:
                 ev['wall_time'] = struct.unpack('<d', v)[0]
@@ -294,7 +354,7 @@ def read_events(path):
                 for f1, _, val in _fields(v):
                     if f1 != 1:
                         continue
-                    tag, sv, im = None, None, None
+                    tag, sv, im, hi = None, None, None, None
                     for f2, _, x in _fields(val):
                         if f2 == 1:
                             tag = x.decode()
@@ -302,7 +362,13 @@ def read_events(path):
                             sv = struct.unpack('<f', x)[0]
                         elif f2 == 4:
                             im = {f3: y for f3, _, y in _fields(x)}
-                    if im is not None:
+                        elif f2 == 5:
+                            hi = {f3: y for f3, _, y in _fields(x)}
+                    if hi is not None:
+                        five = [struct.unpack('<d', hi[k])[0] if k in hi else 0.0 for k in range(1, 6)]
+                        packed = [struct.unpack('<%dd' % (len(hi.get(k, b'')) // 8), hi.get(k, b'')) for k in (6, 7)]
+                        ev['histos'].append((tag,) + tuple(five) + tuple(packed))
+                    elif im is not None:
                         ev['images'].append((tag, im.get(1, 0), im.get(2, 0), im.get(3, 0), bytes(im.get(4, b''))))
                     else:
                         ev['scalars'].append((tag, sv))
