@@ -8,101 +8,41 @@
 // second launch and read by rd_adam_step_guarded and rd_guard_sync through the same device pointer; every launch argument is the
 // same at every step, and the host reads the state only where it synchronises anyway.
 //
-// rd_grad_guard is the health pass of rd_step_log (csrc/step_log.hip; accumulate and wave_sum are common.h's for both) over ONE
-// group: (1) one workgroup per chunk of RD_LOG_CHUNK gradient elements sums g * g in fp64 over its finite elements and counts the
-// others -> partial[chunk]; (2) one wave adds the partials (lane l takes l, l + 64, ... in ascending order, then the fixed xor tree
-// over the lanes) and writes norm, scale, skip and the counters.  Every order is fixed by the indices: no atomics, the same bits on
-// every run.
+// rd_grad_guard is the health pass of rd_step_log (step_log.hip) over ONE group, the whole arena: (1) one workgroup per chunk of
+// RD_LOG_CHUNK gradient elements -> partial[chunk]; (2) one wave folds the partials and writes norm, scale, skip and the counters.
+// The sum itself -- what a chunk and the fold add, in which order, hence every bit -- is the text of sumsq_pass.h for both.
 //
 // rd_guard_sync is ONE launch over range pairs {live, shadow} in the walk of range_walk.h over chunks of RD_GUARD_CHUNK bytes: its
 // lookup, its batched copy of a chunk, its host-side table check.  skip set: live <- shadow (roll the BatchNorm buffers back);
 // otherwise shadow <- live (remember the last good step).
 #include "range_walk.h"
-#include "../../include/ramdsir.h"
+#include "sumsq_pass.h"
 
 namespace {
 
-constexpr int GG_THREADS = 256;
-constexpr int GG_QUADS = RD_LOG_CHUNK / 4 / GG_THREADS;         // 16-byte loads per thread and chunk, all in flight together
-constexpr int GG_FOLD = 8;                                      // partials per lane and pass of the second launch
+using rdsum::Partial;
+constexpr int GG_THREADS = rdsum::THREADS;
 constexpr long long GG_MAX_N = 1ll << 24;                       // rd_step_log's bound: the non-finite count fits any consumer
-static_assert(RD_LOG_CHUNK == GG_QUADS * 4 * GG_THREADS, "a chunk is a whole number of 16-byte loads per thread");
 static_assert(sizeof(rd_guard_state_t) == 40, "rd_guard_state_t is 40 bytes");
-
-struct GuardPartial {
-    double sum;
-    long long count;
-};
 
 // grid (chunks of the arena): partial[chunk] = {sum of squares of the finite elements, number of the others}
 __global__ __launch_bounds__(GG_THREADS) void grad_guard_partial_kernel(const float* __restrict__ grad, long long n,
-                                                                        GuardPartial* __restrict__ partial) {
-    const int c = blockIdx.x, t = threadIdx.x;
+                                                                        Partial* __restrict__ partial) {
+    const int c = blockIdx.x;
     const long long lo = (long long)c * RD_LOG_CHUNK;
     const long long rest = n - lo;
     const int len = rest < RD_LOG_CHUNK ? (int)rest : RD_LOG_CHUNK;
-    const float* __restrict__ p = grad + lo;
-    // [0, head) scalar up to the first 16-byte boundary, then nq whole quads, then [tail, len) scalar: every index is inside the chunk
-    int head = (int)((0 - ((uintptr_t)p >> 2)) & 3);
-    head = head < len ? head : len;
-    const int nq = (len - head) >> 2, tail = head + 4 * nq;
-    const float4* __restrict__ q4 = (const float4*)(p + head);
-    float4 v[GG_QUADS];
-#pragma unroll
-    for (int k = 0; k < GG_QUADS; ++k) {
-        const int q = t + k * GG_THREADS;
-        v[k] = q < nq ? q4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float h = t < head ? p[t] : 0.f;
-    const float e = tail + t < len ? p[tail + t] : 0.f;
-    double s = 0.0;
-    int bad = 0;
-    accumulate(h, s, bad);
-#pragma unroll
-    for (int k = 0; k < GG_QUADS; ++k) {
-        accumulate(v[k].x, s, bad);
-        accumulate(v[k].y, s, bad);
-        accumulate(v[k].z, s, bad);
-        accumulate(v[k].w, s, bad);
-    }
-    accumulate(e, s, bad);
-    __shared__ double s_sum[GG_THREADS / 64];
-    __shared__ long long s_bad[GG_THREADS / 64];
-    s = wave_sum(s);
-    const long long m = wave_sum((long long)bad);
-    if ((t & 63) == 0) { s_sum[t >> 6] = s; s_bad[t >> 6] = m; }
-    __syncthreads();
-    if (t == 0) {
-        GuardPartial r = {s_sum[0], s_bad[0]};
-#pragma unroll
-        for (int w = 1; w < GG_THREADS / 64; ++w) { r.sum += s_sum[w]; r.count += s_bad[w]; }
-        partial[c] = r;
-    }
+    const Partial r = rdsum::chunk(grad + lo, len);
+    if (threadIdx.x == 0) partial[c] = r;
 }
 
 // one wave: fold the partials, lane 0 writes the verdict and the counters
-__global__ __launch_bounds__(64) void grad_guard_final_kernel(const GuardPartial* __restrict__ partial, int chunks, float max_norm,
+__global__ __launch_bounds__(64) void grad_guard_final_kernel(const Partial* __restrict__ partial, int chunks, float max_norm,
                                                               rd_guard_state_t* __restrict__ state) {
     const int lane = threadIdx.x;
-    double s = 0.0;
-    long long bad = 0;
-    // GG_FOLD loads per lane in flight; an absent slot adds 0.0, which leaves the sum as it is, so the order of the additions is the
-    // ascending one whatever GG_FOLD is
-    for (int base = lane; base < chunks; base += 64 * GG_FOLD) {
-        GuardPartial r[GG_FOLD];
-#pragma unroll
-        for (int k = 0; k < GG_FOLD; ++k) {
-            const int i = base + 64 * k;
-            r[k] = i < chunks ? partial[i] : GuardPartial{0.0, 0};
-        }
-#pragma unroll
-        for (int k = 0; k < GG_FOLD; ++k) {
-            s += r[k].sum;
-            bad += r[k].count;
-        }
-    }
-    s = wave_sum(s);
-    bad = wave_sum(bad);
+    const Partial total = rdsum::fold(partial, 0, chunks, lane);
+    const double s = total.sum;
+    const long long bad = total.count;
     if (lane != 0) return;
     const float norm = (float)sqrt(s);
     const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
@@ -141,7 +81,7 @@ __global__ __launch_bounds__(GS_THREADS) void guard_sync_kernel(const rd_guard_r
 }  // namespace
 
 extern "C" int64_t rd_grad_guard_workspace(int64_t n) {
-    return ((n > 0 ? n : 0) + RD_LOG_CHUNK - 1) / RD_LOG_CHUNK * (int64_t)sizeof(GuardPartial);
+    return ((n > 0 ? n : 0) + RD_LOG_CHUNK - 1) / RD_LOG_CHUNK * (int64_t)sizeof(Partial);
 }
 
 extern "C" int rd_grad_guard(const rd_grad_guard_t* p, void* stream) {
@@ -151,8 +91,8 @@ extern "C" int rd_grad_guard(const rd_grad_guard_t* p, void* stream) {
     if (!(p->max_norm >= 0.0f) || p->max_norm > 3.402823466e38f) return -3;         // NaN fails the first comparison, +Inf the second
     const int chunks = (int)((p->n + RD_LOG_CHUNK - 1) / RD_LOG_CHUNK);
     hipStream_t st = (hipStream_t)stream;
-    rd_launch(grad_guard_partial_kernel, dim3(chunks), dim3(GG_THREADS), 0, st, p->grad, (long long)p->n, (GuardPartial*)p->workspace);
-    rd_launch(grad_guard_final_kernel, dim3(1), dim3(64), 0, st, (const GuardPartial*)p->workspace, chunks, p->max_norm, p->state);
+    rd_launch(grad_guard_partial_kernel, dim3(chunks), dim3(GG_THREADS), 0, st, p->grad, (long long)p->n, (Partial*)p->workspace);
+    rd_launch(grad_guard_final_kernel, dim3(1), dim3(64), 0, st, (const Partial*)p->workspace, chunks, p->max_norm, p->state);
     return (int)hipGetLastError();
 }
 

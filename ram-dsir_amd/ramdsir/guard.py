@@ -15,7 +15,7 @@ the verdict in front of Adam and the sync behind the weight repack, and hands Ad
     GradGuard.enqueue_sync(stream)   rd_guard_sync: the roll-back of the BatchNorm buffers or the refresh of their shadows
     GradGuard.read()                 the state word as a dict (synchronises)
     GradGuard.sync_shadow()          shadow <- live, outside the step (at enable time, after a restore)
-    model(grad, max_norm, state)     the numpy model of rd_grad_guard's two launches, in their summation order
+    model(grad, max_norm, state)     the numpy model of rd_grad_guard's two launches, in the summation order of ramdsir/sumsq.py
     GradGuard.named_ranges()         [('guard/state', tensor)] for a training-state snapshot (ramdsir/ckpt.py)
 """
 import ctypes as C
@@ -25,12 +25,11 @@ import torch
 
 from . import _lib as L
 from . import range_table as R
+from .sumsq import CHUNK, fold, partial_sums       # noqa: F401  (the summation order lives there; re-exported for the tests)
 
-CHUNK, THREADS, QUADS = L.LOG_CHUNK, 256, L.LOG_CHUNK // 4 // 256       # rd_grad_guard's first launch (csrc/guard.hip)
 EPS = np.float32(1e-6)
 STATE_FIELDS = tuple(name for name, _ in L.RdGuardState._fields_)
 STATE_BYTES = C.sizeof(L.RdGuardState)
-_LANE = np.arange(64)
 
 
 def workspace_bytes(n):
@@ -46,53 +45,6 @@ def check_max_norm(max_norm):
     return m
 
 
-def _lanes_sum(v):
-    """The xor tree over the 64 lanes (last axis) as the kernels run it: offsets 32, 16, ..., 1; every lane ends with the same bits."""
-    for o in (32, 16, 8, 4, 2, 1):
-        v = v + v[..., _LANE ^ o]
-    return v[..., 0]
-
-
-def _chunk_sums(x, head):
-    """x: float32 [C][len], C chunks of one length; head: words in front of the first 16-byte boundary.  The fp64 sum of squares of
-    each chunk's finite elements in the order of the first launch: per thread the head word, its four quads, the tail word; the
-    64 lanes of each wave in the xor tree; the four waves in ascending order."""
-    Cn, ln = x.shape
-    head = min(head, ln)
-    nq = (ln - head) >> 2
-    tail = head + 4 * nq
-    d = np.where(np.isfinite(x), x, np.float32(0)).astype(np.float64)
-    seq = np.zeros((Cn, THREADS, 2 + 4 * QUADS), np.float64)
-    seq[:, :head, 0] = d[:, :head]
-    quads = np.zeros((Cn, QUADS * THREADS, 4), np.float64)
-    quads[:, :nq] = d[:, head:tail].reshape(Cn, nq, 4)
-    seq[:, :, 1:1 + 4 * QUADS] = quads.reshape(Cn, QUADS, THREADS, 4).transpose(0, 2, 1, 3).reshape(Cn, THREADS, 4 * QUADS)
-    seq[:, :ln - tail, 1 + 4 * QUADS] = d[:, tail:]
-    s = np.zeros((Cn, THREADS), np.float64)
-    for j in range(seq.shape[2]):
-        s = seq[:, :, j] * seq[:, :, j] + s                 # the product of two converted floats is exact in fp64
-    w = _lanes_sum(s.reshape(Cn, THREADS // 64, 64))
-    r = w[:, 0]
-    for k in range(1, THREADS // 64):
-        r = r + w[:, k]
-    return r
-
-
-def partial_sums(grad, align_words=0):
-    """The {sum, count} column pair rd_grad_guard's first launch leaves in its workspace.  align_words: (address of grad / 4) % 4."""
-    g = np.ascontiguousarray(grad, np.float32).reshape(-1)
-    n = g.size
-    head = (-int(align_words)) & 3
-    full = n // CHUNK
-    sums = [_chunk_sums(g[:full * CHUNK].reshape(full, CHUNK), head)] if full else []
-    if n % CHUNK:
-        sums.append(_chunk_sums(g[full * CHUNK:].reshape(1, -1), head))
-    bad = ~np.isfinite(g)
-    chunks = (n + CHUNK - 1) // CHUNK
-    counts = np.add.reduceat(bad.astype(np.int64), np.arange(chunks) * CHUNK)
-    return np.concatenate(sums), counts
-
-
 def scale_of(norm, max_norm):
     """What a step that is not skipped multiplies its gradient by: min(1, max_norm / (norm + 1e-6)) as separately rounded float32
     operations; 1 with max_norm 0."""
@@ -105,18 +57,12 @@ def scale_of(norm, max_norm):
 
 def model(grad, max_norm=0.0, state=None, align_words=0):
     """rd_grad_guard in numpy: the state word after the call, as a dict, from the word before it (None: all zero).  The norm is the
-    float32 of the fp64 square root of the fp64 sum in the kernels' order (lane l of the second launch adds partials l, l + 64, ... in
-    ascending order, then the xor tree); scale is formed from separately rounded float32 operations."""
+    float32 of the fp64 square root of the fp64 sum in the kernels' order (ramdsir/sumsq.py, over the arena as one group); scale is
+    formed from separately rounded float32 operations."""
     f32 = np.float32
     sums, counts = partial_sums(grad, align_words)
-    rows = -(-sums.size // 64)
-    padded = np.zeros(rows * 64, np.float64)
-    padded[:sums.size] = sums
-    s = np.zeros(64, np.float64)
-    for row in padded.reshape(rows, 64):
-        s = s + row
     with np.errstate(all='ignore'):
-        norm = f32(np.sqrt(_lanes_sum(s)))
+        norm = f32(np.sqrt(fold(sums)))
     nonfinite = int(counts.sum())
     skip = nonfinite > 0 or not np.isfinite(norm)
     scale = f32(1) if skip else scale_of(norm, max_norm)

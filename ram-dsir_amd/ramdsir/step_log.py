@@ -8,7 +8,7 @@ non-finite gradient elements) to a ring on the device, and the host drains the r
 
     StepLog.append(stream)   one rd_step_log call; the host owns the row counter
     StepLog.drain()          one device-to-host copy of the pending rows -> one record per iteration
-    model_row(...)           the numpy model of the kernel (float64 sums, non-finite elements masked)
+    model_row(...)           the numpy model of the kernel (float64 sums in the order of ramdsir/sumsq.py, non-finite elements masked)
     rank_mean(rows, group)   data parallel: the mean over the ranks of the loss columns, as FusedTrainer.losses() forms it
 """
 import ctypes as C
@@ -18,15 +18,17 @@ import torch
 
 from . import _lib as L
 from .step import loss_dict_of
+from .sumsq import fold, partial_sums
 
 ROW = L.LOG_ROW
 LOSS, HYPER, REC, NORM, NONFINITE = slice(0, 8), slice(8, 12), slice(12, 28), slice(28, 31), 31       # the words of a row (include/ramdsir.h)
 HEALTH_TAGS = ('health/grad_norm_encoder', 'health/grad_norm_seg_decoder', 'health/grad_norm_rec_decoder', 'health/nonfinite_grads')
 
 
-def model_row(losses, rec_mse, hyper, grads=None, ranges=None):
+def model_row(losses, rec_mse, hyper, grads=None, ranges=None, align_words=0):
     """The row rd_step_log writes, in numpy: grads None -> words 28..31 zero; otherwise per group the float32 of the float64 square root of
-    the float64 sum of squares of its finite elements, and the number of non-finite elements of all three groups."""
+    the float64 sum of squares of its finite elements in the kernels' order (ramdsir/sumsq.py; chunks are counted from the start of the
+    group), and the number of non-finite elements of all three groups.  align_words: (address of grads / 4) % 4."""
     row = np.zeros(ROW, np.float32)
     row[LOSS] = np.asarray(losses, np.float32)
     row[HYPER] = np.asarray(hyper, np.float32)
@@ -40,8 +42,8 @@ def model_row(losses, rec_mse, hyper, grads=None, ranges=None):
             part = g[ranges[k]:ranges[k + 1]]
             finite = np.isfinite(part)
             bad += int(part.size - finite.sum())
-            x = np.where(finite, part, np.float32(0)).astype(np.float64)
-            row[28 + k] = np.float32(np.sqrt(np.sum(x * x, dtype=np.float64)))
+            sums, _ = partial_sums(part, (align_words + ranges[k]) & 3)
+            row[28 + k] = np.float32(np.sqrt(fold(sums)))
         row[NONFINITE] = np.float32(bad)
     return row
 

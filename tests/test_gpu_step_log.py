@@ -3,8 +3,10 @@ model_row), the fused trainer appending a row behind every step without changing
 
 Equality rules.  On gradients that are dyadic rationals (k / 8, |k| <= 16: the squares are multiples of 1 / 64 and every partial sum is an
 integer multiple of 1 / 64 far below 2^53) the fp64 sums are exact in any order, so a row equals the model in every word.  On random
-gradients the fp64 accumulation of n <= 4e6 terms is off by at most n * 2^-53 ~ 4e-10 relative, far below the fp32 half-ulp of 6e-8: the
-stored float32 can differ from float32(sqrt(float64 sum)) only next to a rounding boundary, and then by one ulp."""
+gradients the model restates the kernel's summation order (ramdsir/sumsq.py, given the arena's alignment), so the row equals it there
+as well; the ulp figure is printed.  Only the comparison with torch's norm, which sums in another order, is held to one ulp: the fp64
+accumulation of n <= 4e6 terms is off by at most n * 2^-53 ~ 4e-10 relative, far below the fp32 half-ulp of 6e-8, so the stored
+float32 can differ from float32(sqrt(float64 sum)) only next to a rounding boundary, and then by one ulp."""
 import ctypes as C
 import os
 import subprocess
@@ -79,10 +81,10 @@ def test_random_gradients_within_one_ulp_and_reproducible():
     row, _ = _row(grads, ranges)
     again, _ = _row(grads, ranges)
     assert np.array_equal(_bits(row), _bits(again))
-    want = SL.model_row(LOSSES, REC, HYPER, grads.cpu().numpy(), ranges)
+    want = SL.model_row(LOSSES, REC, HYPER, grads.cpu().numpy(), ranges, align_words=(grads.data_ptr() >> 2) & 3)
     d = np.abs(_bits(row[28:31]).astype(np.int64) - _bits(want[28:31]).astype(np.int64))
     print('norms', row[28:31], 'model', want[28:31], 'ulp', d)
-    assert d.max() <= 1 and row[31] == 0
+    assert d.max() == 0 and row[31] == 0                     # the model is order-exact (ramdsir/sumsq.py): not one ulp, equal
     assert np.array_equal(_bits(row[:28]), _bits(want[:28]))
 
 
