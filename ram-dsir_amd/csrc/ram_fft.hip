@@ -473,6 +473,7 @@ __global__ void ram_mutate_kernel(const float* as, const float* at, float* out, 
 bool make_plan(int N, FftPlan& p) {
     p.N = N;
     p.nst = 0;
+    if (N < 1 || N > 1024) return false;                    // 0 would divide for ever, a large power of 4 overrun radix[]
     int n = N;
     while (n % 4 == 0) { p.radix[p.nst++] = 4; n /= 4; }
     while (n % 2 == 0) { p.radix[p.nst++] = 2; n /= 2; }

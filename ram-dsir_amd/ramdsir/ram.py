@@ -79,6 +79,8 @@ class RamMixer:
         [B,3,H,W] amplitude spectra of the partners instead of their images (trg may then be None)."""
         assert src.is_contiguous() and lam.dtype == torch.float32 and src.dtype in (torch.float32, torch.uint8)
         assert trg is None or (trg.is_contiguous() and trg.dtype == src.dtype)
+        assert trg_amp is None or (trg_amp.is_contiguous() and trg_amp.dtype == torch.float32
+                                   and tuple(trg_amp.shape) == (self.B, 3, self.H, self.W)), 'trg_amp: dense fp32 [B,3,H,W]'
         self.p.src, self.p.lam = src.data_ptr(), lam.data_ptr()
         self.p.trg = trg.data_ptr() if trg is not None else None
         self.p.trg_amp = trg_amp.data_ptr() if trg_amp is not None else None
